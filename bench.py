@@ -11,7 +11,13 @@ BASELINE.json configs[1] (WRN-28-2, K=10, B_l=B_u=512, bf16) per GPU (--scaling 
 GLOBAL batch split over the ranks (--scaling strong: 512/N per loader per rank, BASELINE configs[2]);
 the only data-path collective is one RCCL all-reduce of the flat gradient buffer per step.
 `python bench.py --gpus N` without torchrun starts its own N ranks (fresh processes, one per GPU).
-Prints ONE JSON line (rank 0)."""
+Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own: the
+per-launch roofline passes, the extra keys (config 4, the WRN-28-10 layer table, the other paths of an epoch, the per-rank
+batch table, config 5) and the CPU baseline (each can still be left out with --no-roofline / --no-extras /
+--no-cpu-baseline).  --dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy; that
+step starts from the state before any step, so two runs with the same arguments give it the same inputs."""
 import argparse
 import ctypes
 import json
@@ -40,8 +46,13 @@ def parse():
     ap.add_argument("--classes", type=int, default=10)
     ap.add_argument("--batch", type=int, default=512, help="B_l = B_u per GPU")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beyond the headline figure: roofline passes, extra keys, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all; a fixed, seeded sample of a larger buffer)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-launch roofline passes")
     ap.add_argument("--prof-steps", type=int, default=3)
     ap.add_argument("--graph", type=int, default=None,
                     help="1: replay the step from a captured hipGraph (one stream); 0: issue it eagerly, weight gradients on a "
@@ -57,7 +68,7 @@ def parse():
                          "encoder's backward runs, the encoder bucket after it (dp.DecoderFirstAllReduce) -- the documented "
                          "deviation, to be switched on once an 8-GPU run shows the single exchange is not hidden")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra keys of the headline line (config-4 step, WRN-28-10 layer table)")
+                    help="with --full: skip the extra keys of the headline line (config-4 step, WRN-28-10 layer table)")
     ap.add_argument("--schedule", default="grouped", choices=["grouped", "two-stream", "sequential"],
                     help="grouped (default): the four forwards of the step as one batched launch sequence; two-stream: the "
                          "labelled / unlabelled branches on two HIP streams; sequential: the reference's order, one stream")
@@ -241,6 +252,28 @@ def _time_ms(fn, warm, steps):
     return (time.perf_counter() - t0) / steps * 1e3, out
 
 
+DUMP_BUDGET = 64 << 20            # bytes: every file --dump-outputs writes, together
+DUMP_SAMPLE = 4 << 20             # elements: a longer buffer is written as a sample of this many
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float64 stays float64, everything else becomes float32).  A buffer of more
+    than DUMP_SAMPLE elements is flattened and written at DUMP_SAMPLE positions drawn by numpy's generator with seed 0 from its
+    length alone: the same positions in every run, so that two builds compare element for element."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        x = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        if x.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, DUMP_SAMPLE, replace=False))
+            x = x.reshape(-1)[idx]
+        total += x.nbytes
+        assert total <= DUMP_BUDGET, "--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_BUDGET)
+        np.save(os.path.join(d, name + ".npy"), x)
+
+
 def extras(S):
     """Extra keys of the headline line (same JSON object, the headline fields are untouched), so that they are in the
     driver-written record and not only under profiles/:
@@ -391,15 +424,25 @@ def _multi(world):
     return world > 1 or os.environ.get("SV_DP_SINGLE_RANK") == "1"
 
 
-def svhn_measure(S, B, dtype, steps, warmup, want, multi, rank, init_pg=None):
+def svhn_measure(S, B, dtype, steps, warmup, want, multi, rank, init_pg=None, dump=None):
     """One smooth-ELBO iteration of svhn_VAE at B images per loader on this GPU: eager issue against hipGraph replay
     (want: 1 graph, 0 eager, -1 probe both and keep the faster).  `init_pg`: called AFTER the graph has been captured and
     before anything is timed -- the RCCL process group must not be alive during a stream capture (its watchdog thread polls
-    events), a replay next to it is an ordinary launch; the parameters are broadcast once the group exists."""
+    events), a replay next to it is an ordinary launch; the parameters are broadcast once the group exists.
+    `dump`: a directory for dump_outputs() (rank 0 writes the last timed iteration's loss and Adam state there)."""
     torch.manual_seed(1)
     model = S.SmoothVAE((3, 32, 32), {"cont": 32, "disc": [10]}, temperature=0.67, compute_dtype=dtype).cuda().train()
     loss_fn = S.SmoothELBOLoss()
     opt = S.FlatAdam(model.parameters(), lr=1e-3, capturable=True)
+    start = opt.flat.clone()           # the state the last timed iteration starts from (see reset_state in main)
+
+    def reset():
+        opt.flat.copy_(start)
+        opt.m.zero_()
+        opt.v.zero_()
+        opt.steps = 0
+        if opt.step_dev is not None:
+            opt.step_dev.zero_()
     torch.manual_seed(1 + rank)
     torch.cuda.manual_seed(1 + rank)
     g = torch.Generator(device="cuda").manual_seed(1234 + rank)
@@ -431,10 +474,12 @@ def svhn_measure(S, B, dtype, steps, warmup, want, multi, rank, init_pg=None):
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(fn, n):
+    def timed(fn, n, before_last=None):
         sync()
         t = time.perf_counter()
-        for _ in range(n):
+        for i in range(n):
+            if before_last is not None and i == n - 1:
+                before_last()
             out = fn()
         sync()
         return (time.perf_counter() - t) / n * 1e3, out
@@ -456,7 +501,9 @@ def svhn_measure(S, B, dtype, steps, warmup, want, multi, rank, init_pg=None):
         else:
             mode = "hipGraph replay"
     step = graphed if graphed is not None else eager
-    ms, loss = timed(step, steps)
+    ms, loss = timed(step, steps, before_last=reset)
+    if dump and rank == 0:
+        dump_outputs(dump, {"loss": loss, "params": opt.flat, "adam_m": opt.m, "adam_v": opt.v})
     dt = torch.tensor([ms], device="cuda", dtype=torch.float64)
     if multi:
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
@@ -472,7 +519,8 @@ def svhn_workload(a, rank, world, init_pg):
     import shot_vae_amd as S
     multi = _multi(world)
     B = a.batch if a.scaling == "weak" else a.batch // world
-    r = svhn_measure(S, B, a.dtype, a.steps, a.warmup, a.graph if a.graph is not None else -1, multi, rank, init_pg)
+    r = svhn_measure(S, B, a.dtype, a.steps, a.warmup, a.graph if a.graph is not None else -1, multi, rank, init_pg,
+                     dump=a.dump_outputs)
     ms, mode, probe = r["ms"], r["mode"], r["probe"]
     assert r["finite"], "non-finite loss"
     # algorithmic work: 1.1332e7 MACs per forwarded image, x3 for forward + both gradients, x2 flop per MAC
@@ -603,6 +651,19 @@ def main():
         model._engine.fork_every = a.fork_every
     dmode = False if not multi else ("bucketed" if a.allreduce == "bucketed" else True)
 
+    # The LAST timed step starts from the state before any step (the same seeded weights on every rank), restored in front of
+    # it inside the timed window: three buffer copies, once per run.  The default mode's atomic sums differ in the last bits
+    # from run to run, and bf16 training turns that into visibly different weights within a few steps; without the reset two
+    # runs with the same arguments would give the step that --dump-outputs records different inputs.
+    eng0 = model._engine
+    start = [t.clone() for t in (eng0.param, eng0.bufs, eng0.nbt)]
+
+    def reset_state():
+        for t, s in zip((eng0.param, eng0.bufs, eng0.nbt), start):
+            t.copy_(s)
+        opt._steps = 0                    # sv_sgd's first-step form, v = d: the momentum buffer's old content is not read
+        eng0.mark_dirty()
+
     mode = a.graph if a.graph is not None else (-1 if a.scaling == "strong" else 0)
     graphed, graph_note, probe = None, "eager, weight gradients on a side stream", None
     if mode and a.schedule != "sequential":
@@ -659,7 +720,9 @@ def main():
         step()
     sync()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for i in range(a.steps):
+        if i == a.steps - 1:
+            reset_state()
         ls, lu = step()
     sync()
     dt = time.perf_counter() - t0
@@ -668,6 +731,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t)
     assert torch.isfinite(ls).all() and torch.isfinite(lu).all(), "non-finite loss"
+    if a.dump_outputs and rank == 0:
+        # the last timed step's losses and the state it left: parameters and SGD momentum (the flat buffers sv_sgd updates;
+        # the gradient buffer is zeroed behind the update) and the BatchNorm running statistics
+        bn = [b.reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()]
+        dump_outputs(a.dump_outputs, {"loss_sup": ls, "loss_unsup": lu, "params": model._engine.param,
+                                      "momentum": model._engine.mom, "bn_running_stats": torch.cat(bn)})
     # the lambda contract: every rank used the same mixup coefficients in the last step
     lam_equal = None
     lams = getattr(model, "_last_lams", None)
@@ -724,7 +793,7 @@ def main():
         out["config"]["lambda_equal_across_ranks"] = lam_equal
 
     # ---- roofline: HIP events around EVERY launch of the library (separate single-stream passes of the same step) ----
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         eng = model._engine
         peak_t = MFMA_PEAK_TFLOPS[a.dtype]
 
@@ -844,11 +913,11 @@ def main():
                             tag_, r["name"], r["launches"] // a.prof_steps, r["avg_us"], r["total_ms"] / a.prof_steps,
                             "%.1f" % (r["bytes"] / r["avg_us"] / 1e3) if r["bytes"] else "-",
                             "%.2f" % (r["flops"] / r["avg_us"] / 1e6) if r["flops"] else "-"), file=sys.stderr)
-    if rank == 0 and world == 1 and headline and a.dtype == "bf16" and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and headline and a.dtype == "bf16" and not a.no_extras:
         del model, opt, graphed
         torch.cuda.empty_cache()
         out.update(extras(S))
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.net, K)
     if multi:
         dist.barrier()

@@ -44,3 +44,33 @@ def test_bench_rejects_mismatched_world_size():
     r = _run("--gpus", "4", "--dry-run", env=dict(WORLD_SIZE="2", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                                                   MASTER_PORT="29999"))
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
+
+
+def test_bench_has_the_full_and_dump_options():
+    r = _run("--help")
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout, r.stderr[-2000:]
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_long_buffers_the_same_way(tmp_path):
+    """bench.py --dump-outputs: float64 stays, everything else is float32; a buffer longer than DUMP_SAMPLE is written at the
+    same seeded positions in every run; more than DUMP_BUDGET bytes in all is refused."""
+    import numpy as np
+    import pytest
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(bench.DUMP_SAMPLE + 1000, dtype=torch.float32)
+    arrays = {"loss": torch.tensor(1.5), "wide": torch.arange(3, dtype=torch.float64),
+              "half": torch.full((10,), 0.5, dtype=torch.bfloat16), "big": big}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in arrays}
+    assert got["loss"].dtype == np.float32 and float(got["loss"]) == 1.5
+    assert got["wide"].dtype == np.float64 and got["wide"].tolist() == [0.0, 1.0, 2.0]
+    assert got["half"].dtype == np.float32 and (got["half"] == 0.5).all()
+    s = got["big"]
+    assert s.dtype == np.float32 and s.size == bench.DUMP_SAMPLE
+    assert (np.diff(s) > 0).all() and s[0] >= 0 and s[-1] < big.numel()       # distinct positions, in order
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.npy"))
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "c"), {"b%d" % i: big for i in range(5)})

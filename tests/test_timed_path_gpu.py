@@ -285,3 +285,46 @@ def test_smooth_vae_iteration_at_config5_size():
     for _ in range(5):
         last = float(S.smooth_train_step(model, loss_fn, opt, unl.cuda(), lab.cuda(), label.cuda()))
     assert np.isfinite(last) and last < float(loss)
+
+
+@pytest.mark.parametrize("workload,names", [
+    ("shotvae", ["bn_running_stats", "loss_sup", "loss_unsup", "momentum", "params"]),
+    ("svhn", ["adam_m", "adam_v", "loss", "params"])])
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path, workload, names):
+    """bench.py without --full: the timed steps only (none of the keys --full adds), `steps` as asked, and --dump-outputs
+    writes the last timed step's losses and state -- the losses in the files are the ones in the JSON line.  Two runs with the
+    same arguments give that step the same inputs, so their outputs agree to the default mode's rounding (measured at full
+    size: relative L2 <= 5e-7, no element off by more than 2e-6 of the array's largest)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for rep in ("a", "b"):
+        args = ["--workload", workload, "--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / rep)]
+        if workload == "svhn":
+            args += ["--batch", "64"]
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + args, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]))
+    out = runs[0]
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0
+    assert not {"roofline", "cpu_baseline", "config4", "wrn28_10_layer_table", "headline_variants", "config5"} & set(out)
+    d = tmp_path / "a"
+    assert sorted(f[:-4] for f in os.listdir(d)) == names
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+    arrays = {n: np.load(d / (n + ".npy")) for n in names}
+    for n, x in arrays.items():
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all(), n
+    assert arrays["params"].size > 1000 and np.abs(arrays["params"]).max() > 0
+    if workload == "shotvae":
+        assert round(float(arrays["loss_sup"]), 5) == out["loss_sup"]
+        assert round(float(arrays["loss_unsup"]), 5) == out["loss_unsup"]
+    else:
+        assert round(float(arrays["loss"]), 4) == out["loss"]
+    for n, x in arrays.items():
+        x, y = x.astype(np.float64), np.load(tmp_path / "b" / (n + ".npy")).astype(np.float64)
+        scale = max(float(np.abs(x).max()), 1e-30)
+        assert float(np.linalg.norm(x - y)) <= 1e-5 * max(float(np.linalg.norm(x)), 1e-30), n
+        assert float(np.abs(x - y).max()) <= 1e-4 * scale, n

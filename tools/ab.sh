@@ -24,6 +24,6 @@ for v in "$@"; do
     continue
   fi
   (cd "$R" && export SV_LIB_PATH="$LIBV"
-   SV_BENCH_TABLE=1 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2> /tmp/ab.table | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config 2:', d['ms_per_step'], 'ms', d['value'])"; grep -E "$TAGS" /tmp/ab.table | awk '{printf "   %-30s %8.1f us\n",$2,$6}'
-   if [ -n "$SV_AB_C4" ]; then SV_BENCH_TABLE=1 python bench.py --net wideresnet-28-10 --classes 100 --batch 256 --steps 10 --warmup 3 --no-cpu-baseline 2> /tmp/ab4.table | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config 4:', d['ms_per_step'], 'ms', d['value'])"; grep -E "$TAGS" /tmp/ab4.table | awk '{printf "   %-30s %8.1f us\n",$2,$6}'; fi)
+   SV_BENCH_TABLE=1 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2> "$R/build/ab/table" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config 2:', d['ms_per_step'], 'ms', d['value'])"; grep -E "$TAGS" "$R/build/ab/table" | awk '{printf "   %-30s %8.1f us\n",$2,$6}'
+   if [ -n "$SV_AB_C4" ]; then SV_BENCH_TABLE=1 python bench.py --full --net wideresnet-28-10 --classes 100 --batch 256 --steps 10 --warmup 3 --no-cpu-baseline 2> "$R/build/ab/table4" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('config 4:', d['ms_per_step'], 'ms', d['value'])"; grep -E "$TAGS" "$R/build/ab/table4" | awk '{printf "   %-30s %8.1f us\n",$2,$6}'; fi)
 done

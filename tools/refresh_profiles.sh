@@ -7,7 +7,7 @@ PMC=$2
 OUT="$R/gpurun_out/profiles_new"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-python3 "$R/bench.py" --steps 30 --warmup 10 2>/dev/null | tail -1 > "$OUT/${TAG}_bench.json"
+python3 "$R/bench.py" --full --steps 30 --warmup 10 2>/dev/null | tail -1 > "$OUT/${TAG}_bench.json"
 rm -rf /tmp/prof_b
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_b -o b -- python3 "$R/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-extras --wgrad-side 0 > /tmp/prof_b.log 2>&1
 F=$(find /tmp/prof_b -name "*kernel_stats.csv" | head -1)
@@ -18,8 +18,8 @@ python3 "$R/tools/kernel_stats_digest.py" "$F" 13 "rocprofv3 --kernel-trace --st
 { for s in "3 2 1024 160 32 320" "3 2 1024 320 16 640" "1 2 1024 160 32 320" "1 2 1024 320 16 640" "3 1 1024 16 32 160" "1 1 1024 16 32 160"; do
     set -- $s; SV_BENCH_K=$1 SV_BENCH_S=$2 python3 "$R/tools/layer_bench.py" $3 $4 $5 $6; done; } 2>/dev/null | grep "of bf16" > "$OUT/${TAG}_layer_bench_odd.txt"
 set -- "$TAG" "$PMC"
-SV_BENCH_TABLE=1 python3 "$R/bench.py" --steps 20 --warmup 5 --no-cpu-baseline 2> "$OUT/${TAG}_bench_kernel_table.txt" > /dev/null
-SV_BENCH_TABLE=1 python3 "$R/bench.py" --net wideresnet-28-10 --batch 256 --classes 100 --steps 10 --warmup 3 --no-cpu-baseline 2> "$OUT/${TAG}_cfg4_wrn28_10_kernel_table.txt" | tail -1 > "$OUT/${TAG}_cfg4_wrn28_10_bench.json"
+SV_BENCH_TABLE=1 python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline 2> "$OUT/${TAG}_bench_kernel_table.txt" > /dev/null
+SV_BENCH_TABLE=1 python3 "$R/bench.py" --full --net wideresnet-28-10 --batch 256 --classes 100 --steps 10 --warmup 3 --no-cpu-baseline 2> "$OUT/${TAG}_cfg4_wrn28_10_kernel_table.txt" | tail -1 > "$OUT/${TAG}_cfg4_wrn28_10_bench.json"
 rm -rf /tmp/prof_c
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_c -o c -- python3 "$R/bench.py" --net wideresnet-28-10 --batch 256 --classes 100 --steps 6 --warmup 2 --no-cpu-baseline --no-roofline --wgrad-side 0 > /tmp/prof_c.log 2>&1
 F=$(find /tmp/prof_c -name "*kernel_stats.csv" | head -1)
