@@ -47,27 +47,12 @@ constexpr int LDF = 48;     // LDS row of the dy halo and of the activated input
                             // the 16-byte fragment reads (conv3x3.hip) and for the transposing 8-byte reads (wgrad3x3.hip)
 constexpr int LDR = 40;     // LDS row of the raw input (80 bytes: the epilogue's 8-byte reads of 16 pixels hit 16 bank pairs)
 constexpr int CH = 32;
-// Fragment sets of the weight-gradient waves (compute_g): 1 = all ten fragments of a 32-pixel chunk at once (40 registers), 2 = two
-// groups of 5 + 4 taps (24), 3 = two full sets, double-buffered (80).  Measured alone at 4 x 512 images (tools/probes/bwdf_ablate.sh,
-// round 6, loader = the weight-gradient waves only): plain 125 / 115 / 121 us with 2 / 1 / 3; two-tensor 143 / 143 / 143.
-#ifndef SV_BWDF_FRAGS
-#define SV_BWDF_FRAGS 1
-#endif
 // 16-channel tiles of the data gradient whose weight fragments live in registers (36 each); the others are read from LDS
 #ifndef SV_BWDF_WREGS
 #define SV_BWDF_WREGS 2
 #endif
 // timing ablations (tools/probes/bwdf_ablate.sh; results wrong by construction): 1 = no weight-gradient MFMAs, 2 = no data-gradient
 // MFMAs / epilogue, 4 = no global loads in the loop, 8 = no staging (transform + LDS stores), 16 = data gradient without its epilogue
-// order of an iteration: 1 = the wave stages the next tile BEFORE its MFMAs.  Data-gradient waves: always (computing first: two-tensor
-// form 167 vs 149 us, residual form 253 vs 158).  Weight-gradient waves (-1 = by form): behind their MFMAs where dy is a tensor (123 vs
-// 126 us), in front of them in the two- and three-tensor forms (138 vs 149, 156 vs 158 us; tools/probes/bwdf_ablate.sh, round 6)
-#ifndef SV_BWDF_DFIRST
-#define SV_BWDF_DFIRST 1
-#endif
-#ifndef SV_BWDF_GFIRST
-#define SV_BWDF_GFIRST -1
-#endif
 #ifndef SV_BWDF_ABL
 #define SV_BWDF_ABL 0
 #endif
@@ -131,8 +116,14 @@ __global__ __launch_bounds__(512) void bwd3x3f_kernel(const sv_geom g, const bwd
     typedef bf16x8 V;
     typedef bf16x4 Q;
     constexpr int WREGS = WLOG == 5 ? SV_BWDF_WREGS : (MODE == 0 ? 1 : 0);      // (the variants that do not spill)
-    constexpr int FRAGS = WLOG == 5 ? SV_BWDF_FRAGS : 2;                       // fragment sets of the weight-gradient waves
-    constexpr bool GFIRST = SV_BWDF_GFIRST < 0 ? MODE >= 1 : SV_BWDF_GFIRST != 0;
+    // fragment sets of the weight-gradient waves (compute_g): 1 = all ten fragments of a 32-pixel chunk at once (40 registers), 2 = two
+    // groups of 5 + 4 taps (24).  Measured alone at 4 x 512 images (tools/probes/bwdf_ablate.sh, round 6, loader = the weight-gradient
+    // waves only): plain 125 / 115 us with 2 / 1; two-tensor 143 / 143.  (Two full sets, double-buffered, 80 registers: 121 / 143 us.)
+    constexpr int FRAGS = WLOG == 5 ? 1 : 2;
+    // order of an iteration: the wave stages the next tile BEFORE its MFMAs.  Data-gradient waves: always (computing first: two-tensor
+    // form 167 vs 149 us, residual form 253 vs 158).  Weight-gradient waves: behind their MFMAs where dy is a tensor (123 vs 126 us),
+    // in front of them in the two- and three-tensor forms (138 vs 149, 156 vs 158 us; tools/probes/bwdf_ablate.sh, round 6)
+    constexpr bool GFIRST = MODE >= 1;
     constexpr int WLROWS = (2 - WREGS) * 16 * 9;       // LDS rows of weights [c][tap] of the tiles that are not register-resident
     constexpr int W = 1 << WLOG, TR = 128 / W, WP = W + 2;
     // LDS halo rows: row 0 / the last row are the vertical halo; when a tile holds two whole images (W = 8) a zero spacer row
@@ -376,11 +367,10 @@ __global__ __launch_bounds__(512) void bwd3x3f_kernel(const sv_geom g, const bwd
     auto compute_g = [&](int stage) __attribute__((always_inline)) {
         const bf16* dyh = st0 + stage * STG;
         const bf16* ac = dyh + SDY;
-        // fragments of one 32-pixel chunk: the activated-input fragment + the nine tap-shifted dy fragments, requested together
-        // and double-buffered over the chunks (wgrad3x3_kernel)
-        // fragments of one 32-pixel chunk: the activated-input fragment + the tap-shifted dy fragments in two groups (5 + 4 taps):
-        // the reads of a group are issued right behind the MFMAs of the group before (which have read their operands at issue) and
-        // return while the matrix pipe works those off; a full second set (wgrad3x3_kernel) cost 40 registers, all ten fragments 16
+        // fragments of one 32-pixel chunk: the activated-input fragment + the nine tap-shifted dy fragments, all at once (FRAGS 1) or
+        // in two groups of 5 + 4 taps (FRAGS 2): the reads of a group are issued right behind the MFMAs of the group before (which have
+        // read their operands at issue) and return while the matrix pipe works those off; a full second set (wgrad3x3_kernel) cost 40
+        // registers, all ten fragments 16
         auto frag_b = [&](int kc) __attribute__((always_inline)) {
             const int pq = 32 * kc + 8 * fq + (fr >> 2);          // the lane addresses pixel pq of the tile (and pq + 4)
             return ftr(ac, pq * LDF, 16 * wj, lane);
@@ -391,27 +381,7 @@ __global__ __launch_bounds__(512) void bwd3x3f_kernel(const sv_geom g, const bwd
             const int hb = ((jrow + 1 + jrow / HH) * WP + xcol + 1) * LDF;
             return ftr(dyh, hb + ((1 - t / 3) * WP + (1 - t % 3)) * LDF, 16 * wi, lane);
         };
-        if constexpr (FRAGS == 3) {
-            // two fragment sets, double-buffered over the chunks (wgrad3x3_kernel)
-            bf16x8 fbA, faA[9], fbB, faB[9];
-            auto ld = [&](bf16x8& fb, bf16x8 (&fa)[9], int kc) __attribute__((always_inline)) {
-                fb = frag_b(kc);
-#pragma unroll
-                for (int t = 0; t < 9; ++t) fa[t] = frag_a(kc, t);
-            };
-            auto mm = [&](const bf16x8& fb, const bf16x8 (&fa)[9]) __attribute__((always_inline)) {
-#pragma unroll
-                for (int t = 0; t < 9; ++t) dacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[t], fb, dacc[t], 0, 0, 0);
-            };
-            ld(fbA, faA, 0);
-            ld(fbB, faB, 1);
-            mm(fbA, faA);
-            ld(fbA, faA, 2);
-            mm(fbB, faB);
-            ld(fbB, faB, 3);
-            mm(fbA, faA);
-            mm(fbB, faB);
-        } else if constexpr (FRAGS == 1) {
+        if constexpr (FRAGS == 1) {
 #pragma unroll
             for (int kc = 0; kc < 4; ++kc) {
                 const bf16x8 fb = frag_b(kc);
@@ -453,10 +423,9 @@ __global__ __launch_bounds__(512) void bwd3x3f_kernel(const sv_geom g, const bwd
     if (wave < 4) {
         bwdf_stage<1, MODE> SA, SB;
         auto iter = [&](int tile, int stage, bwdf_stage<1, MODE>& S) __attribute__((always_inline)) {
-            if (!SV_BWDF_DFIRST && !(SV_BWDF_ABL & 2)) compute_d(tile, stage);
             if (!(SV_BWDF_ABL & 8)) store_stage(S, min(tile + tstep, t_last), stage ^ 1);
             if (!(SV_BWDF_ABL & 4)) load_stage(S, min(tile + 3 * tstep, t_last));
-            if (SV_BWDF_DFIRST && !(SV_BWDF_ABL & 2)) compute_d(tile, stage);
+            if (!(SV_BWDF_ABL & 2)) compute_d(tile, stage);
             tile_barrier();
         };
         load_stage(SA, t_begin);

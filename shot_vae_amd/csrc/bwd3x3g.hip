@@ -42,12 +42,6 @@ constexpr size_t LDS_BYTES = (size_t)2 * STG * 2 + 2 * CH * 8 + 8 * CH * 4 + (si
 #ifndef SV_BWDG_WREG01
 #define SV_BWDG_WREG01 1        // (2: 177-186 spilled registers)
 #endif
-#ifndef SV_BWDG_HSTG2
-#define SV_BWDG_HSTG2 0        // (1: 135 vs 126 us -- slower)
-#endif
-#ifndef SV_BWDG_DPP
-#define SV_BWDG_DPP 1
-#endif
 #ifndef SV_BWDG_ABL
 #define SV_BWDG_ABL 0        // timing ablations as in bwd3x3f.hip: 1 no weight-gradient MFMAs, 2 no data gradient, 4 no loads, 8 no staging, 16 no epilogue
 #endif
@@ -279,7 +273,7 @@ __global__ __launch_bounds__(512) void bwd3x3g_kernel(const sv_geom g, const bwd
         // Pixel fragments: a 16-pixel fragment is a WHOLE image row (W = 16), so the fragments of the taps left and right of the centre
         // column are the centre fragment moved by one lane with ZERO coming in at the end of the row (the convolution's padding):
         // one LDS read + two DPP row shifts per (kernel row, k-step, pixel tile) instead of three reads -- 12 instead of 36 pixel-fragment
-        // reads per tile and wave on a kernel that is bound by the LDS port (SV_BWDG_DPP 0: three reads).  Bit-identical operands.
+        // reads per tile and wave on a kernel that is bound by the LDS port.  Bit-identical operands.
         constexpr int PD = SV_BWDG_PD, NB = PD + 1;
         V fw0[NWR >= 1 ? 1 : NB], fw1[NWR >= 2 ? 1 : NB];
         V pc[2][2][2];                              // [buffer][k-step][pixel tile]: the centre-column fragments of a kernel row
@@ -314,15 +308,8 @@ __global__ __launch_bounds__(512) void bwd3x3g_kernel(const sv_geom g, const bwd
             if (s_ % 6 == 0 && ty < 2) rdp(ty + 1);
             if (s_ + PD < 18) rdw(s_ + PD);
             __builtin_amdgcn_sched_barrier(0);
-            V a0, a1;
-            if (SV_BWDG_DPP) {
-                a0 = shifted(pc[ty & 1][k][0], tx);
-                a1 = shifted(pc[ty & 1][k][1], tx);
-            } else {
-                const int sh = ((1 - ty) * WP + (1 - tx)) * LDF + 32 * k;
-                a0 = *reinterpret_cast<const V*>(dyh + hbase[0] + sh);
-                a1 = *reinterpret_cast<const V*>(dyh + hbase[1] + sh);
-            }
+            const V a0 = shifted(pc[ty & 1][k][0], tx);
+            const V a1 = shifted(pc[ty & 1][k][1], tx);
             const V w0 = NWR >= 1 ? wr[0][s_] : fw0[NWR >= 1 ? 0 : b];
             const V w1 = NWR >= 2 ? wr[NWR >= 2 ? 1 : 0][s_] : fw1[NWR >= 2 ? 0 : b];
             mma32(acc[0][0], w0, a0);
@@ -415,25 +402,23 @@ __global__ __launch_bounds__(512) void bwd3x3g_kernel(const sv_geom g, const bwd
         }
         // ONE register stage (bwd3x3f.hip has two): a tile takes ~3 us here, the request issued at the top of an iteration has a whole
         // iteration to arrive -- and the second stage's 24 / 48 / 72 registers are what the register-resident weights need
-        // (SV_BWDG_HSTG2: a second stage in the residual form, whose six tensor passes make it the HBM-bound one)
-        constexpr bool TWO = MODE == 2 && SV_BWDG_HSTG2;
-        bwdg_halo<MODE> S, S2;
-        auto iter = [&](int tile, int stage, bwdg_halo<MODE>& Q_) __attribute__((always_inline)) {
-            if (!(SV_BWDG_ABL & 8)) store_halo(Q_, min(tile + tstep, t_last), stage ^ 1);
-            if (!(SV_BWDG_ABL & 4)) load_halo(Q_, min(tile + (TWO ? 3 : 2) * tstep, t_last));
+        // (a second stage in the residual form, whose six tensor passes make it the HBM-bound one: 135 vs 126 us -- slower)
+        bwdg_halo<MODE> S;
+        auto iter = [&](int tile, int stage) __attribute__((always_inline)) {
+            if (!(SV_BWDG_ABL & 8)) store_halo(S, min(tile + tstep, t_last), stage ^ 1);
+            if (!(SV_BWDG_ABL & 4)) load_halo(S, min(tile + 2 * tstep, t_last));
             if (!(SV_BWDG_ABL & 2)) compute_d(tile, stage);
             tile_barrier();
         };
         load_halo(S, t_begin);
-        if (TWO) load_halo(S2, min(t_begin + tstep, t_last));
         __syncthreads();                                      // the coefficient vectors and the weights in LDS
         store_halo(S, t_begin, 0);
-        load_halo(S, min(t_begin + (TWO ? 2 : 1) * tstep, t_last));
+        load_halo(S, min(t_begin + tstep, t_last));
         __syncthreads();                                      // tile t_begin staged
         int tile = t_begin;
         for (int k = 0; k + 1 < n_tiles; k += 2, tile += 2 * tstep) {
-            iter(tile, 0, TWO ? S2 : S);
-            iter(tile + tstep, 1, S);
+            iter(tile, 0);
+            iter(tile + tstep, 1);
         }
         if (n_tiles & 1) {
             if (!(SV_BWDG_ABL & 2)) compute_d(tile, 0);

@@ -12,21 +12,9 @@
 #include "common.h"
 #include "epilogue.h"
 
-#ifndef SV_C3P_WREG
-#define SV_C3P_WREG 1
-#endif
-#ifndef SV_C3P_INTERLEAVE
-#define SV_C3P_INTERLEAVE 1    // tile order of the persistent kernel: 1 = all blocks sweep one moving window, 0 = a contiguous range per block
-#endif
 #ifndef SV_C3P_DEPTH
 #define SV_C3P_DEPTH 2         // register stages of the halo (request distance in tiles); 3: one more stage, operands two tiles ahead
                                // (measured: data gradient 92 -> 96 / 169 us without / with the weights in registers -- spills)
-#endif
-#ifndef SV_C3P_EOP_AHEAD
-#define SV_C3P_EOP_AHEAD 1     // the epilogue operand of a tile is requested one tile ahead (0: inside its own tile)
-#endif
-#ifndef SV_C3P_MODES
-#define SV_C3P_MODES 1         // fusion flags of conv3x3p at compile time for the step's three launch kinds (0: run-time flags only)
 #endif
 #ifndef SV_C3P_WAVES
 #define SV_C3P_WAVES 2          // waves per SIMD the persistent kernel is compiled for (3 => spills, measured slower)
@@ -241,16 +229,16 @@ __global__ __launch_bounds__(256, SV_C3P_WAVES) void conv3x3p_kernel(const sv_ge
     if (NC % 8 == 0) {
         const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
         in_i = slot % nNt;
-        xsub = SV_C3P_INTERLEAVE ? xcd * (NC / 8) + slot / nNt : (slot / nNt) * 8 + xcd;
+        xsub = xcd * (NC / 8) + slot / nNt;
     } else {
         in_i = blockIdx.x % nNt;
         xsub = blockIdx.x / nNt;
     }
     const int n0 = in_i * BN;
     // step k of this block: tile k * tstep + t_begin, while it is < t_end
-    const int tstep = SV_C3P_INTERLEAVE ? NC : 1;
-    const int t_begin = SV_C3P_INTERLEAVE ? xsub : xsub * tiles_per;
-    const int t_end = SV_C3P_INTERLEAVE ? nT : min(nT, t_begin + tiles_per);
+    const int tstep = NC;
+    const int t_begin = xsub;
+    const int t_end = nT;
     if (t_begin >= t_end) return;
     const sv_phase& P = g.phase[0];
     const uint64_t pdy = pack_taps(P.dy), pdx = pack_taps(P.dx);
@@ -376,7 +364,7 @@ __global__ __launch_bounds__(256, SV_C3P_WAVES) void conv3x3p_kernel(const sv_ge
     __syncthreads();
     // 32 input channels: the block's 18 weight fragments stay in registers (72 of them: with the fusion flags at compile time
     // the variants hold 152-176 without) -- the nine taps read only the pixel fragments from LDS
-    constexpr bool WREG = SV_C3P_WREG && CCH == 1 && sizeof(T) == 2 && MODE != 0;
+    constexpr bool WREG = CCH == 1 && sizeof(T) == 2 && MODE != 0;
     V wr[WREG ? 9 : 1][NT];
     if (WREG) {
 #pragma unroll
@@ -405,7 +393,7 @@ __global__ __launch_bounds__(256, SV_C3P_WAVES) void conv3x3p_kernel(const sv_ge
     };
     EStage EA, EB, EC;
     constexpr int HD = SV_C3P_DEPTH, ED = SV_C3P_DEPTH - 1;      // request distances in tiles: halo, epilogue operand
-    if (SV_C3P_EOP_AHEAD && (hasR || hasEX)) {
+    if (hasR || hasEX) {
         load_eop(EA, t_begin);
         if (ED == 2 && t_begin + tstep < t_end) load_eop(EB, t_begin + tstep);
     }
@@ -415,8 +403,7 @@ __global__ __launch_bounds__(256, SV_C3P_WAVES) void conv3x3p_kernel(const sv_ge
         // ---- request the halo HD tiles ahead + the epilogue operands ED tiles ahead; they fly during the MFMAs ----
         const bool more = tile + tstep < t_end;
         if (tile + HD * tstep < t_end) load_halo(FREE, tile + HD * tstep);
-        if (SV_C3P_EOP_AHEAD) { if (tile + ED * tstep < t_end && (hasR || hasEX)) load_eop(ENEXT, tile + ED * tstep); }
-        else if (hasR || hasEX) load_eop(ECUR, tile);
+        if (tile + ED * tstep < t_end && (hasR || hasEX)) load_eop(ENEXT, tile + ED * tstep);
         Q (&eop)[NT][2] = ECUR.v;
         int64_t obase[2];
 #pragma unroll
@@ -813,14 +800,12 @@ int launch_pm(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
 // the three launch kinds of the training step take the binaries with their fusion flags at compile time (bf16 only)
 template <typename T, int WLOG, int CCH>
 int launch_p(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
-#if SV_C3P_MODES
     if constexpr (sizeof(T) == 2) {
         if (!a->bias) {
             if (a->pro_scale && a->stats && !a->ex) return a->residual ? launch_pm<T, WLOG, CCH, 2>(g, a, s) : launch_pm<T, WLOG, CCH, 1>(g, a, s);
             if (!a->pro_scale && a->ex && !a->residual && !a->stats) return launch_pm<T, WLOG, CCH, 3>(g, a, s);
         }
     }
-#endif
     return launch_pm<T, WLOG, CCH, 0>(g, a, s);
 }
 

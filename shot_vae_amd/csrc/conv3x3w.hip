@@ -31,10 +31,6 @@
 #define SV_W3_EPD 1
 #endif
 
-#ifndef SV_W3_MODES
-#define SV_W3_MODES 1
-#endif
-
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -406,7 +402,6 @@ int launch_w4(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
 // at compile time; every other shape / flag combination the run-time-flag binary
 template <int NF, int WLOG, bool REV>
 int launch_w3(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
-#if SV_W3_MODES
     if constexpr (NF == 4 && WLOG == 3) {
         if (!a->bias) {
             if constexpr (REV) {
@@ -417,7 +412,6 @@ int launch_w3(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
             }
         }
     }
-#endif
     return launch_w4<NF, WLOG, REV, 0>(g, a, s);
 }
 

@@ -7,9 +7,6 @@
     // SV_EPI_NSCR scratch sets per wave (1 or 2): with two, consecutive groups use different LDS.  SV_EPI_BASE = byte offset
     // of the scratch in LDS (0: over the dead halo / weight buffers; a persistent kernel keeps it apart).  SV_EPI_ALIAS:
     // the per-wave reduction buffer lies over the (by then consumed) transpose scratch of the same wave.
-#ifndef SV_EPI_DPP
-#define SV_EPI_DPP 1        // the per-channel sums cross the four lanes of a DPP row before they go through LDS
-#endif
     constexpr int NSCR = SV_EPI_NSCR, EBASE = SV_EPI_BASE;
     constexpr bool EALIAS = SV_EPI_ALIAS != 0;
     constexpr int ERED = EALIAS ? 0 : 4 * NSCR * 4096;
@@ -149,10 +146,9 @@
         //  move below, nothing of the reduction above the next group's dump)
         asm volatile("" ::: "memory");
         if (want_stats || has_EX) {
-#if SV_EPI_DPP
             // 16 partial sums per lane, 16 lanes (pixel rows) per channel group cg = lane & 3.  First across the four lanes of a DPP row
             // that share cg (two row_shr steps: lanes 12..15 of a row then hold the row's sums), only those lanes go through LDS:
-            // a quarter of the scratch traffic of the all-through-LDS form below and 4 instead of 16 dependent reads per lane
+            // a quarter of the scratch traffic of an all-through-LDS form and 4 instead of 16 dependent reads per lane
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 s1[e] += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, s1[e]), 0x114, 0xf, 0xf, true));
@@ -175,20 +171,6 @@
             float t = 0.f;
 #pragma unroll
             for (int q = 0; q < 4; ++q) t += col[16 * q];
-#else
-            // 16 partial sums per lane, 16 lanes per channel group: through LDS -- lane (group cg', sum e') adds the 16
-            // pixel rows of its column (4 b128 stores + 16 b32 loads + 16 adds instead of 64 shuffles + 64 adds)
-            float* mine = red + (cg * 16 + ipix) * 16;
-#pragma unroll
-            for (int q4 = 0; q4 < 2; ++q4) {
-                *reinterpret_cast<f32x4*>(mine + 4 * q4) = f32x4{s1[4 * q4], s1[4 * q4 + 1], s1[4 * q4 + 2], s1[4 * q4 + 3]};
-                *reinterpret_cast<f32x4*>(mine + 8 + 4 * q4) = f32x4{s2[4 * q4], s2[4 * q4 + 1], s2[4 * q4 + 2], s2[4 * q4 + 3]};
-            }
-            const float* col = red + (lane >> 4) * 256 + (lane & 15);
-            float t = 0.f;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) t += col[16 * q];
-#endif
             const int e2 = lane & 15;
             // SV_EPI_WAVE_SUMS: every wave owns a copy of the sums (each address is written once per item and wave: a plain
             // store, nothing to clear, no LDS float atomics); otherwise the four waves meet in one copy

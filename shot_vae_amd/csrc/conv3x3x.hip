@@ -40,23 +40,6 @@
 // directly in front of MFMAs 0, 2, ... and produced wrong even rows; the run-time-flag binary had the same exposure and was
 // right by luck of its allocation.  Every MFMA therefore carries its own `s_nop 1` (measured: not slower -- 320 / 299 us
 // against 337 / 308 at 160 channels).
-#ifndef SV_X3_NOP
-#define SV_X3_NOP 1
-#endif
-#if SV_X3_NOP
-#define SV_X3_PRE "s_nop 1\n\t"
-#else
-#define SV_X3_PRE
-#endif
-#ifndef SV_X3_DRAIN
-#define SV_X3_DRAIN 1      // 1: the epilogue's stores have left before the K loop resumes
-#endif
-#ifndef SV_X3_DMAH
-#define SV_X3_DMAH 1       // data gradients without a load prologue: the halo by LDS-DMA (make_xsched_dma)
-#endif
-#ifndef SV_X3_MODES
-#define SV_X3_MODES 2      // epilogue fusion flags at compile time: 1 = for the forward launch kinds, 2 = and the data gradient; 0 = run-time flags only
-#endif
 
 #ifndef SV_X3_STAMP
 #define SV_X3_STAMP 0      // diagnostic build: (s_memrealtime, s_memtime) of every block at start / after the prologue / after every K loop / after every epilogue
@@ -551,7 +534,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3x_kernel(const sv_geom g, const
             constexpr int t = decltype(T)::value, tn = (t + 1) % 9;
             static_for<20>([&](auto M) {
                 constexpr int m = decltype(M)::value, ks = m / 10, i = (m % 10) / 2, f = m & 1;
-                asm volatile(SV_X3_PRE "v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc[f][i]) : "v"(A[ks][i]), "v"(Bf[ks][f]));
+                asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(acc[f][i]) : "v"(A[ks][i]), "v"(Bf[ks][f]));
                 static_for<6>([&](auto JJ) {
                     constexpr int code = SCHED.item[20 * t + m][decltype(JJ)::value];
                     if constexpr (code >= 1000 && code < 2000)
@@ -643,10 +626,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3x_kernel(const sv_geom g, const
 #undef SV_EPI_BASE
 #undef SV_EPI_ALIAS
             }
-            // (SV_X3_DRAIN = 0: outstanding stores only make the loop's counted waits conservative -- a wait for a register load
-            //  counts the younger register loads, which retire after it: with the load outstanding the counter is above the count)
-            if (SV_X3_DRAIN) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            // the epilogue's stores have left before the K loop resumes (outstanding, they would only make the loop's counted waits
+            // conservative -- a wait for a register load counts the younger register loads, which retire after it)
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             if (item < 5) SV_X3_STAMP_AT(3 + 2 * item);
       }
       {   // step to the next item's first chunk (staged during this item's last one)
@@ -685,24 +667,19 @@ int launch_x4(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
 }
 
 // forward launches come with statistics (+ residual), data gradients with the activation-backward epilogue; anything else
-// (bias, no statistics, ...) takes the binary that reads the flags at run time
+// (bias, no statistics, ...) takes the binary that reads the flags at run time.  Data gradients without a load prologue take
+// the halo by LDS-DMA (make_xsched_dma).
 template <int WLOG, bool REV>
 int launch_x3(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
-#if SV_X3_MODES
     if (!a->bias) {
         if constexpr (REV) {
-#if SV_X3_MODES > 1
-#if SV_X3_DMAH
             if (a->ex && !a->residual && !a->pro_scale && g->ldx % 8 == 0) return launch_x4<WLOG, REV, 3, true>(g, a, s);
-#endif
             if (a->ex && !a->residual) return launch_x4<WLOG, REV, 3>(g, a, s);
-#endif
         } else {
             if (a->stats && a->residual && !a->ex) return launch_x4<WLOG, REV, 2>(g, a, s);
             if (a->stats && !a->residual && !a->ex) return launch_x4<WLOG, REV, 1>(g, a, s);
         }
     }
-#endif
     return launch_x4<WLOG, REV, 0>(g, a, s);
 }
 

@@ -33,13 +33,6 @@ namespace {
 // Blocks per CU of the small-stage persistent variants (measured at 4 x 512 images, tools/thin_ab.sh: three blocks of the
 // 2-vector / 16-channel-tile variant: stem 66 -> 55 us, 1x1 16 -> 32 data gradient 54 -> 46 us; four blocks or any of the
 // 32-channel-tile variants spill -- 16 -> 32 forward 115 -> 176 / 290 us -- and stay at two)
-#ifndef SV_HALOP_EO_AHEAD
-#define SV_HALOP_EO_AHEAD 0    // 1: the epilogue operand of a tile is requested one tile ahead (measured mixed here: -4 % .. +6 % per layer, step flat;
-                                // conv3x3p, one block per CU in the paired backward, gains 17 % from the same change)
-#endif
-#ifndef SV_HALOP_MODES
-#define SV_HALOP_MODES 1
-#endif
 #ifndef SV_HALOP_OCC2
 #define SV_HALOP_OCC2 3         // 2-vector stage, 16-channel tiles (NT = 1)
 #endif
@@ -600,11 +593,10 @@ __global__ __launch_bounds__(256, OCC) void halop_kernel(const sv_geom g, const 
     if (t_begin + 1 < t_end) load_halo(HB, t_begin + 1);
     store_halo(HA);
     __syncthreads();
-    // the epilogue's extra operand (residual OR raw tensor) of every (phase, row, channel group) of a tile is requested ONE TILE
-    // AHEAD (clamped addresses: rows / channel groups beyond the tensor read a valid element and are not stored).  Requested
-    // inside the epilogue it was an exposed round trip per tile (waves of the thin layers waited 70 % of their cycles,
-    // tools/pmc_sq.py); requested at the top of its own tile, behind the halo of tile + 2, it still made the epilogue wait for
-    // that halo -- loads return in order (conv3x3p: data gradient 112 -> 93 us with the same change).
+    // the epilogue's extra operand (residual OR raw tensor) of every (phase, row, channel group) of a tile is requested at the top
+    // of its tile, behind the halo of tile + 2 (clamped addresses: rows / channel groups beyond the tensor read a valid element
+    // and are not stored).  Requested inside the epilogue it was an exposed round trip per tile (waves of the thin layers waited
+    // 70 % of their cycles, tools/pmc_sq.py).  (One tile ahead, as in conv3x3p: mixed here, -4 % .. +6 % per layer, step flat.)
     struct EStage { Q eo[NPH][2][NT]; };
     auto load_eo = [&](EStage& E, int tile) {
         const int R0 = tile * c.TR;
@@ -627,14 +619,12 @@ __global__ __launch_bounds__(256, OCC) void halop_kernel(const sv_geom g, const 
         }
     };
     EStage EA, EB;
-    if (SV_HALOP_EO_AHEAD && (hasR || hasEX)) load_eo(EA, t_begin);
-    auto do_tile = [&](int tile, HStage& NEXT, HStage& FREE, EStage& ECUR, EStage& ENEXT) {
+    auto do_tile = [&](int tile, HStage& NEXT, HStage& FREE, EStage& E) {
         const int R0 = tile * c.TR;
         const bool more = tile + 1 < t_end;
         if (tile + 2 < t_end) load_halo(FREE, tile + 2);              // flies during this tile's and the next tile's MFMAs
-        if (SV_HALOP_EO_AHEAD) { if (more && (hasR || hasEX)) load_eo(ENEXT, tile + 1); }
-        else if (hasR || hasEX) load_eo(ECUR, tile);
-        Q (&eo)[NPH][2][NT] = ECUR.eo;
+        if (hasR || hasEX) load_eo(E, tile);
+        Q (&eo)[NPH][2][NT] = E.eo;
         int64_t obv[NPH][2];
         bool rokv[2];
 #pragma unroll
@@ -712,8 +702,8 @@ __global__ __launch_bounds__(256, OCC) void halop_kernel(const sv_geom g, const 
         __syncthreads();                               // the next halo is visible
     };
     for (int tile = t_begin; tile < t_end; tile += 2) {
-        do_tile(tile, HB, HA, EA, EB);
-        if (tile + 1 < t_end) do_tile(tile + 1, HA, HB, EB, EA);
+        do_tile(tile, HB, HA, EA);
+        if (tile + 1 < t_end) do_tile(tile + 1, HA, HB, EB);
     }
     if (want_sums) flush_channel_sums<NT>(s1, s2, nval, ssum, hasEX ? a.bsums : a.stats, n0, g.N, a.replicas, a.flags);
 }
@@ -774,7 +764,6 @@ int launch_halop_m(const sv_geom* g, const sv_igemm_args* a, const halo_cfg& c, 
 // the two launch kinds the step issues most take the binaries with their fusion flags at compile time (bf16)
 template <typename T, int NT, int CC, int NPH>
 int launch_halop(const sv_geom* g, const sv_igemm_args* a, const halo_cfg& c, size_t lds, hipStream_t s) {
-#if SV_HALOP_MODES
     if constexpr (sizeof(T) == 2) {
         if (!a->bias && !a->residual) {
             if (a->pro_scale && a->stats && !a->ex) return launch_halop_m<T, NT, CC, NPH, 1>(g, a, c, lds, s);
@@ -782,7 +771,6 @@ int launch_halop(const sv_geom* g, const sv_igemm_args* a, const halo_cfg& c, si
             if (!a->pro_scale && a->ex && !a->stats) return launch_halop_m<T, NT, CC, NPH, 3>(g, a, c, lds, s);
         }
     }
-#endif
     return launch_halop_m<T, NT, CC, NPH, 0>(g, a, c, lds, s);
 }
 

@@ -180,9 +180,6 @@ static bnb_params_g bnb_expand(const bnb_params& p, int groups, int es) {
     return A;
 }
 
-#ifndef SV_BNB_UNROLL2
-#define SV_BNB_UNROLL2 0        // 1: two vectors per trip of sv_bn_bwd_apply's loop (twice the bytes in flight; measured no gain: 43.1 vs 43.4 us, tools/probes/small_ab.sh)
-#endif
 // REG: (threads of the grid) % (C/8) == 0, so a thread always meets the same 8 channels and keeps their
 // coefficients [gamma*rstd, mean(g), mean(g*xhat)] (+ mean, rstd) in registers; otherwise they sit in LDS.
 template <typename T, bool REG>
@@ -337,19 +334,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bnb_params_g PG
         *reinterpret_cast<V*>(DX + mm * p.ld + cc) = ov;
     };
     int64_t i = gtid;
-    if (REG && SV_BNB_UNROLL2) {
-        // two vectors per trip, the second one's loads issued before the first one's arithmetic: twice the bytes in flight per
-        // thread (the kernel runs one resident wave of blocks, 5 waves per SIMD: ~60 KB per CU in flight with one vector per trip,
-        // at the edge of what the HBM latency needs)
-        for (; i + gsz < total; i += 2 * gsz) {
-            V xa, ga[2], ra, xb, gb[2], rb_;
-            fetch(m, c, xa, ga, ra);
-            fetch(m + m_step, c, xb, gb, rb_);
-            apply(m, c, xa, ga, ra);
-            apply(m + m_step, c, xb, gb, rb_);
-            m += 2 * m_step;
-        }
-    }
+    // (two vectors per trip, twice the bytes in flight: no gain, 43.1 vs 43.4 us)
     for (; i < total; i += gsz) {
         V xv, gv[2], rv;
         fetch(m, c, xv, gv, rv);

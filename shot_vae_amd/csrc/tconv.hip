@@ -32,20 +32,11 @@
 #ifndef SV_TCONVR_DBG
 #define SV_TCONVR_DBG 0         // ablation switches (tools/probes/tconvr_ablate.sh): 1 no MFMA loop, 2 no output stores, 4 no next-image load / staging, 8 no statistics, 16 no LDS fragment reads
 #endif
-#ifndef SV_TCONVR_PIPE
-#define SV_TCONVR_PIPE 1        // the epilogue of a pixel tile in the MFMA gaps of the other one (see the kernel)
-#endif
-#ifndef SV_TCONVR_PIPE_STAGE
-#define SV_TCONVR_PIPE_STAGE 0  // 1: ... and the staging of the next image in the gaps of the second tile's MFMAs (measured WORSE: 46.5-48 vs 44.7 us -- the wait for the vectors and 16 spilled registers land inside the MFMA stream)
-#endif
 #ifndef SV_TCONVX16_TP
 #define SV_TCONVX16_TP 2        // pixel tiles per pass of the 16 x 16 data-gradient kernel (1: 85.8 vs 83.8 us)
 #endif
-#ifndef SV_TCONVR_WMAP
-#define SV_TCONVR_WMAP 0        // 1: (phase, tile) = (wave >> 1, wave & 1) instead of (wave & 3, wave >> 2)
-#endif
 #ifndef SV_TCONVR_KL
-#define SV_TCONVR_KL (SV_TCONVR_PIPE ? 12 : 8)   // of a wave's 32 A fragments the last KL are read from LDS (the registers they would take spill otherwise)
+#define SV_TCONVR_KL 12         // of a wave's 32 A fragments the last KL are read from LDS (the registers they would take spill otherwise)
 #endif
 #ifndef SV_TCONVR_PD
 #define SV_TCONVR_PD 2          // the B fragments are requested this many groups ahead of their MFMAs
@@ -88,8 +79,8 @@ __global__ __launch_bounds__(512, 1) void tconvr_kernel(const sv_geom g, const s
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // this wave's phase and 32-channel tile (EX: phases 3 3 1 1 0 0 2 2 -- waves w and w + 4 share a SIMD: 4 + 1 and 2 + 2 taps)
-    const int ph = EX ? (0x22001133 >> (4 * wave)) & 3 : (SV_TCONVR_WMAP ? wave >> 1 : wave & 3);
-    const int nt = EX ? wave & 1 : (SV_TCONVR_WMAP ? wave & 1 : wave >> 2);
+    const int ph = EX ? (0x22001133 >> (4 * wave)) & 3 : wave & 3;
+    const int nt = EX ? wave & 1 : wave >> 2;
     const int q = lane & 31, h = lane >> 5;
     const sv_phase& P = g.phase[ph];
     const bf16* __restrict__ X = reinterpret_cast<const bf16*>(a.x);
@@ -242,7 +233,7 @@ __global__ __launch_bounds__(512, 1) void tconvr_kernel(const sv_geom g, const s
     // share a SIMD's vector issue, and a second wave's VALU stream got no slots beside the first wave's back-to-back MFMAs
     // (running the two waves of a SIMD in opposite order, epilogue-then-MFMA against MFMA-then-epilogue, changed nothing: 44.0
     // vs 43.4 us).  What does hide is vector work placed in the issue gaps of the wave's OWN MFMAs (an MFMA holds the vector
-    // issue for 8 of its 32 cycles): SV_TCONVR_PIPE = 1, below.
+    // issue for 8 of its 32 cycles): the pipelined epilogue below.
     f32x16 acc[MT];
     // acc[mt][4 gq + e] = channel 32 nt + 8 gq + 4 h + e of pixel q of tile mt.  Stores widened to 16 bytes: v_permlane32_swap
     // hands the upper half-wave's channels 8 gq + 4 .. 7 to the lower one and the lower half-wave's channels 8 (gq + 1) .. + 3 to
@@ -272,26 +263,6 @@ __global__ __launch_bounds__(512, 1) void tconvr_kernel(const sv_geom g, const s
             const u32x4 o = {pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
             bf16* const oimg = O + (int64_t)im * ostride;
             if (!(SV_TCONVR_DBG & 2) || o[0] == 0x12345678u) *reinterpret_cast<u32x4*>(oimg + mt * otile + opix + 16 * (e >> 3)) = o;
-        }
-    };
-    // SV_TCONVR_PIPE: the staging of the next image too, in 8 steps -- element e of the thread's vectors (one channel: one
-    // {scale, shift} pair from LDS, requested a step ahead) -- and the two LDS stores behind the last one
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 cq[2];
-    auto stg_fetch = [&](int e) { cq[e & 1] = *reinterpret_cast<const f32x2*>(coef + 16 * sc + 2 * e); };
-    auto stg_step = [&](int e, int buf) {
-        if (has_pro) {
-            const f32x2 c = cq[e & 1];
-            if (e + 1 < 8) stg_fetch(e + 1);
-#pragma unroll
-            for (int i = 0; i < VPT; ++i) {
-                const float u = (float)xr[i][e] * c[0] + c[1];
-                xr[i][e] = (bf16)fmaxf(u, u * slope);
-            }
-        }
-        if (e == 7) {
-#pragma unroll
-            for (int i = 0; i < VPT; ++i) *reinterpret_cast<bf16x8*>(smem + buf * TILE + sdst + i * (4 * PITCH * 32)) = xr[i];
         }
     };
     auto epilogue = [&](int mt, int im) {
@@ -351,11 +322,12 @@ __global__ __launch_bounds__(512, 1) void tconvr_kernel(const sv_geom g, const s
             }
         }
     };
-    // SV_TCONVR_PIPE: the two pixel tiles of an image run one after the other (32 MFMAs each on one accumulator set), and the
-    // epilogue of the tile that has just finished rides in the MFMA gaps of the other one -- tile 1 of image i - 1 under tile 0
-    // of image i (its accumulators stay live across the barrier), tile 0 of image i under tile 1: no second accumulator set.
+    // The two pixel tiles of an image run one after the other (32 MFMAs each on one accumulator set), and the epilogue of the
+    // tile that has just finished rides in the MFMA gaps of the other one -- tile 1 of image i - 1 under tile 0 of image i (its
+    // accumulators stay live across the barrier), tile 0 of image i under tile 1: no second accumulator set.  (The staging of
+    // the next image in the gaps of the second tile's MFMAs as well: worse, 46.5-48 vs 44.7 us -- the wait for the vectors
+    // and 16 spilled registers land inside the MFMA stream.)
     // bufc: LDS image of image im; prevc: tile 1 of image `prev` awaits its epilogue
-    constexpr bool PIPE_STAGE = (SV_TCONVR_PIPE != 0) && (SV_TCONVR_PIPE_STAGE != 0);
     auto body = [&](auto bufc, auto prevc, int im, int prev) __attribute__((always_inline)) {
         constexpr int BUF = decltype(bufc)::value;
         constexpr bool PREV = decltype(prevc)::value;
@@ -366,7 +338,7 @@ __global__ __launch_bounds__(512, 1) void tconvr_kernel(const sv_geom g, const s
         // the B fragments of step i + PD are requested before the MFMA(s) of step i; the scheduling barrier keeps the compiler
         // from hoisting all 64 reads to the front (256 registers, spilled)
         constexpr int PD = SV_TCONVR_PD, NB = PD + 1;           // request distance in k-steps, ring of NB fragment sets
-        constexpr int TPS = SV_TCONVR_PIPE ? 1 : MT;            // pixel tiles per pass over the k-steps
+        constexpr int TPS = 1;                                  // pixel tiles per pass over the k-steps (the other one: epilogue)
 #pragma unroll
         for (int pass = 0; pass < MT / TPS; ++pass) {
             bf16x8 bfr[NB][TPS], afr[NB];
@@ -396,27 +368,16 @@ __global__ __launch_bounds__(512, 1) void tconvr_kernel(const sv_geom g, const s
 #pragma unroll
                 for (int i = 0; i < TPS; ++i)
                     acc[pass * TPS + i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ks < KR ? wf[ks < KR ? ks : 0] : afr[ks % NB], bfr[ks % NB][i], acc[pass * TPS + i], 0, 0, 0);
-                if (SV_TCONVR_PIPE && (ks & 1)) {      // one element of the other tile per two k-steps
+                if (ks & 1) {      // one element of the other tile per two k-steps
                     if (pass == 1) epi_step(0, ks >> 1, im);
                     else if (PREV) epi_step(1, ks >> 1, prev);
-                }
-                if (PIPE_STAGE && pass == 1 && (ks & 3) == 0 && !(SV_TCONVR_DBG & 4)) {
-                    // (second pass: the vectors requested at the start of the interval have had a whole pass to arrive)
-                    if (has_next) {
-                        if (ks == 0 && has_pro) stg_fetch(0);
-                        stg_step(ks >> 2, BUF ^ 1);
-                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
         stamp(2);
-        if (!SV_TCONVR_PIPE) {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) epilogue(mt, im);
-        }
         stamp(3);
-        if (has_next && !(SV_TCONVR_DBG & 4) && !PIPE_STAGE) stage(BUF ^ 1);
+        if (has_next && !(SV_TCONVR_DBG & 4)) stage(BUF ^ 1);
         stamp(4);
         __syncthreads();
         stamp(5);
@@ -471,7 +432,7 @@ __global__ __launch_bounds__(512, 1) void tconvr_kernel(const sv_geom g, const s
             img += step;
         }
     } else {
-        static_assert(!SV_TCONVR_PIPE || (MT == 2 && KS == 32), "pipelined epilogue: 16 elements over 32 k-steps, two tiles");
+        static_assert(MT == 2 && KS == 32, "pipelined epilogue: 16 elements over 32 k-steps, two tiles");
         using T0 = std::integral_constant<int, 0>;
         using T1 = std::integral_constant<int, 1>;
         const int step = gridDim.x;
@@ -490,7 +451,7 @@ __global__ __launch_bounds__(512, 1) void tconvr_kernel(const sv_geom g, const s
                 img += step;
             }
         }
-        if (SV_TCONVR_PIPE && last >= 0) epilogue(1, last);
+        if (last >= 0) epilogue(1, last);
     }
     if ((SV_TCONVR_DBG & 32) && a.fold_mean && blockIdx.x == 0 && blockIdx.y == 0 && lane == 0) {
         unsigned long long* const dbg = reinterpret_cast<unsigned long long*>(a.fold_mean) + wave * 8;

@@ -1,9 +1,10 @@
 #!/bin/bash
-# Variants of the 16x16 data-gradient kernel of tconv.hip (-DSV_TCONVX16_TP=2, -DSV_TCONVR_PD=1, ...): rebuild, relink, time.  GPU box.
+# Variants of the 16x16 data-gradient kernel of tconv.hip (-DSV_TCONVX16_TP=1, -DSV_TCONVR_PD=1, ...): scratch libraries
+# (tools/ab_build.sh) selected with SV_LIB_PATH, the layer timed.  GPU box.
 R="$(cd "$(dirname "$0")/../.." && pwd)"
-cd "$R/shot_vae_amd/csrc"
+n=0
 for flags in "$@"; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -munsafe-fp-atomics -I$R/include $flags -c tconv.hip -o tconv.o 2>/dev/null
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC igemm.o halo.o tconv.o sconv.o pconv.o dconv.o thconv.o thwgrad.o s2wgrad.o hwgrad.o conv3x3.o conv3x3w.o conv3x3x.o wgrad.o wgrad3x3.o small.o runtime.o -o ../libshotvae_hip.so
-  echo -n "[$flags]  "; SV_BENCH_S=2 python3 $R/tools/layer_bench.py 2048 32 32 64 2>&1 | grep "dgrad" | head -1
+  n=$((n + 1))
+  LIBV=$(bash "$R/tools/ab_build.sh" tconv.hip "tconvx16_$n" $flags) || exit 1
+  echo -n "[$flags]  "; SV_LIB_PATH="$LIBV" SV_BENCH_S=2 python3 $R/tools/layer_bench.py 2048 32 32 64 2>&1 | grep "dgrad" | head -1
 done

@@ -1,13 +1,12 @@
-cd shot_vae_amd/csrc
-FLAGS="--offload-arch=gfx950 -O3 -fPIC -std=c++17 -munsafe-fp-atomics -I../../include -Wno-unused-function"
-mkdir -p ../../build/ab
-OBJS=""; for o in igemm halo hwgrad conv3x3 conv3x3w wgrad wgrad3x3 small runtime; do OBJS="$OBJS $o.o"; done
+#!/bin/bash
+# conv3x3x.hip: residual rows in flight in the epilogue (SV_X3_EPD = 1 / 2 / 3), built into scratch libraries
+# (tools/ab_build.sh) and timed on the wide layers.  GPU box.
+R="$(cd "$(dirname "$0")/../.." && pwd)"
+cd "$R"
 for v in 1 2 3; do
-  /opt/rocm/bin/hipcc $FLAGS -DSV_X3_EPD=$v -c conv3x3x.hip -o ../../build/ab/x3e$v.o 2>/dev/null && /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC ../../build/ab/x3e$v.o $OBJS -o ../../build/ab/lib_x3e$v.so &
+  bash tools/ab_build.sh conv3x3x.hip "x3e$v" -DSV_X3_EPD=$v > /dev/null || exit 1
 done
-wait
-cd ../..
 for v in 1 2 3; do
   echo "== EPD=$v"
-  SV_LIB_PATH=$PWD/build/ab/lib_x3e$v.so python tools/layer_bench.py 2>&1 | grep "of bf16" | grep -v wgrad
+  SV_LIB_PATH="$R/build/ab/lib_x3e$v.so" python tools/layer_bench.py 2>&1 | grep "of bf16" | grep -v wgrad
 done
