@@ -2,6 +2,7 @@
 
 fp32 mode (exact-fp32 MFMA) must agree to ~1e-4 of the tensor scale; bf16 mode to 2e-2 (operand
 rounding; SURVEY.md §8d tolerances)."""
+import copy
 import ctypes as C
 
 import numpy as np
@@ -1854,3 +1855,193 @@ def test_folded_batchnorm_finalisation(dt, B, Cin, N, H, k, stride, groups, R, h
     wt = bq(master, dt).view(N, k, k, Cin).permute(0, 3, 1, 2)
     ref = F.conv2d(act, wt, None, stride, pad)
     assert rel(nchw(o1[:B]), ref) < max(tol, 3e-3)
+
+
+# ------------------------------------------------------------------------------------------------ evaluation / BN-apply kernels
+def _topk_ref(score, label, k):
+    """rank of the label under a stable descending sort (float64): ties go to the lower class index"""
+    order = torch.sort(score.double(), dim=1, descending=True, stable=True).indices
+    rank = (order == label[:, None]).int().argmax(1)
+    return int((rank < 1).sum()), int((rank < k).sum())
+
+
+@pytest.mark.parametrize("k", [1, 5])
+@pytest.mark.parametrize("K", [10, 100])
+@pytest.mark.parametrize("B", [1, 257, 20000])          # 20 000 rows > the 64-block grid: the grid-stride loop
+def test_topk_hits_against_stable_sort(B, K, k):
+    g = torch.Generator().manual_seed(B + K + k)
+    lv = 4 if K == 10 else 24
+    score = torch.randint(0, lv, (B, K), generator=g).float() / lv         # a few levels: ties everywhere
+    label = torch.randint(0, K, (B,), generator=g)
+    for r in range(0, B, 3):                    # ties with the label's own score at a lower and at a higher index
+        y = int(label[r])
+        if y > 0:
+            score[r, (y * 7 + r) % y] = score[r, y]
+        if y < K - 1:
+            score[r, y + 1 + (r % (K - 1 - y))] = score[r, y]
+    h1, hk = _topk_ref(score, label, k)
+    assert 0 < h1 < B or B == 1
+    d = dev()
+    hits = torch.tensor([3.0, 5.0], device=d)
+    sd, ld = score.to(d), label.to(d)
+    for _ in range(2):                          # accumulates
+        L.call("sv_topk_hits", p(sd), p(ld), B, K, k, p(hits), st())
+    L.call("sv_topk_hits", p(sd), p(ld), 0, K, k, p(hits), st())         # B = 0 leaves hits untouched
+    torch.cuda.synchronize()
+    assert hits.cpu().tolist() == [3.0 + 2 * h1, 5.0 + 2 * hk]
+
+
+@pytest.mark.parametrize("Cn", [16, 300])               # 300: two blocks
+def test_bn_eval_affine_against_float64(Cn):
+    g = torch.Generator().manual_seed(Cn)
+    gamma, beta, rm = torch.randn(Cn, generator=g), torch.randn(Cn, generator=g), torch.randn(Cn, generator=g)
+    rv = torch.rand(Cn, generator=g) * 3 + 1e-3
+    eps = 1e-5
+    d = dev()
+    scale, shift = torch.full((Cn,), float("nan"), device=d), torch.full((Cn,), float("nan"), device=d)
+    L.call("sv_bn_eval_affine", Cn, p(gamma.to(d)), p(beta.to(d)), p(rm.to(d)), p(rv.to(d)), eps, p(scale), p(shift), st())
+    torch.cuda.synchronize()
+    want_s = gamma.double() / torch.sqrt(rv.double() + eps)
+    want_t = beta.double() - rm.double() * want_s
+    # [1.2e-7] (rsqrtf)
+    assert rel(scale, want_s) < 1e-6 and rel(shift, want_t) < 1e-6, (rel(scale, want_s), rel(shift, want_t))
+
+
+@pytest.mark.parametrize("slope", [0.0, 0.01])
+@pytest.mark.parametrize("Cn", [8, 24, 640])
+@pytest.mark.parametrize("groups", [1, 3])
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+def test_bn_act_against_float64(dt, groups, Cn, slope):
+    code, tdt, _ = DT[dt]
+    M = 37 if Cn == 640 else 129                        # odd row counts
+    g = torch.Generator().manual_seed(Cn + groups)
+    x = torch.randn(groups, M, Cn, generator=g).to(tdt)
+    s, t = torch.randn(groups, Cn, generator=g), torch.randn(groups, Cn, generator=g)     # per-group scale / shift
+    d = dev()
+    out = torch.full((groups, M, Cn), float("nan"), dtype=tdt, device=d)
+    L.call("sv_bn_act", code, p(x.to(d)), p(s.to(d)), p(t.to(d)), slope, M, Cn, p(out), groups, st())
+    torch.cuda.synchronize()
+    u = x.double() * s.double()[:, None, :] + t.double()[:, None, :]
+    want = torch.where(u > 0, u, slope * u)
+    got = out.cpu()
+    assert not torch.isnan(got.float()).any()
+    if dt == "f32":
+        assert rel(got, want) < 1e-6, rel(got, want)           # [4.6e-8]
+    else:                                               # the bf16 rounding of the reference, within one bf16 ulp
+        r = want.to(torch.bfloat16).double()
+        a = torch.maximum(r.abs(), got.double().abs()).clamp_min(2.0 ** -126)
+        ulp = torch.exp2(torch.floor(torch.log2(a)) - 7)
+        assert bool(((got.double() - r).abs() <= ulp + 1e-6 * float(want.abs().max())).all())
+
+
+# ------------------------------------------------------------------------------------------------ smooth-ELBO parameter tables
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("kind,shape", [("svhn", (3, 32, 32)), ("mnist", (1, 32, 32))])
+def test_param_gather_and_scatter_add_against_torch(kind, shape, dt):
+    """sv_param_gather / sv_param_scatter_add run the job tables tests/test_smooth_plan_cpu.py emulates: every layer's packs
+    (Conv2d OIHW, ConvTranspose2d IOHW, the permuted Linear layers, the shared heads) against an explicit float64 re-layout of
+    the parameter, the padded biases, and the gradient scatter against `+=` into the parameters' .grad"""
+    import shot_vae_amd as S
+    from shot_vae_amd import smooth as SM
+    from tests.test_smooth_plan_cpu import _expected_weights, _master
+    d = dev()
+    torch.manual_seed(6)
+    ref = S.SmoothVAE(shape, {"cont": 20, "disc": [10]}, use_cuda=False, kind=kind, compute_dtype="fp32" if dt == "f32" else "bf16")
+    for prm in ref.parameters():
+        prm.data.normal_()
+    model = copy.deepcopy(ref).to(d)
+    ref = ref.double()                                  # the float64 statement of the same parameters
+    params = list(model.parameters())
+    g0 = [torch.randn(prm.shape, device=d) for prm in params]
+    for prm, gg in zip(params, g0):
+        prm.grad = gg.clone()
+    plan = SM._WeightPlan(model, d)
+    plan._build(model, False)
+    plan._build(model, True)
+    tdt = DT[dt][1]
+    pack = torch.zeros(plan.pack.numel(), dtype=tdt, device=d)
+    bias = torch.zeros(plan.bias.numel(), device=d)
+    raw, n, nb = plan.wjobs
+    L.call("sv_param_gather", DT[dt][0], p(raw), n, nb, p(pack), st())
+    raw, n, nb = plan.bjobs
+    L.call("sv_param_gather", L.SV_F32, p(raw), n, nb, p(bias), st())
+    torch.cuda.synchronize()
+    packs, biases = pack.double().cpu(), bias.double().cpu()
+    exp = {k: (w.detach(), b.detach()) for k, (w, b) in _expected_weights(ref).items()}
+    for name, layer in model._L.items():
+        w, b = exp[name]
+        m = _master(layer, w)                                               # [N][tap][Cin], float64, zero padded
+        geoms = [(0, plan.fwd_off[name], layer.geom_fwd(1))]
+        if name in plan.dg_off:
+            geoms.append((1, plan.dg_off[name], layer.geom_dgrad(1)))
+        for transpose, off, gm in geoms:
+            for ph in range(gm.nphase):
+                P = gm.phase[ph]
+                if not P.ntap:
+                    continue
+                sel = m[:, [P.torig[tp] for tp in range(P.ntap)], :]
+                want = (sel.permute(2, 1, 0) if transpose else sel).reshape(-1).to(tdt).double()
+                got = packs[off + P.w_off: off + P.w_off + want.numel()]
+                assert torch.equal(got, want), (name, transpose, ph)
+        want_b = torch.zeros(layer.N, dtype=torch.float64)
+        want_b[: layer.n_real] = b.float().double()
+        assert torch.equal(biases[plan.bias_off[name]: plan.bias_off[name] + layer.N], want_b), name
+    # scatter: master-layout gradients (bias gradients of some layers as the next layer's DOUBLE sums) += into .grad
+    gr = torch.Generator().manual_seed(1)
+    scr = torch.zeros(plan.gscr.numel())
+    dws, dbs = {}, {}
+    for name, layer in model._L.items():
+        dws[name] = torch.randn(layer.N, layer.T, layer.Cin, generator=gr)
+        dbs[name] = torch.randn(layer.N, generator=gr)
+        scr[plan.dw_off[name]: plan.dw_off[name] + dws[name].numel()] = dws[name].reshape(-1)
+        nxt = SM.BIAS_FROM_NEXT.get(name)
+        if nxt is None:
+            scr[plan.db_off[name]: plan.db_off[name] + layer.N] = dbs[name]
+        else:
+            scr[plan.bs_off[nxt]: plan.bs_off[nxt] + 2 * layer.N].view(torch.float64)[:] = dbs[name].double()
+    raw, n, nb = plan.gjobs
+    L.call("sv_param_scatter_add", p(raw), n, nb, p(scr.to(d)), st())
+    torch.cuda.synchronize()
+    cpu = list(ref.parameters())
+    total = 0.0
+    exp = _expected_weights(ref)
+    for name, layer in ref._L.items():
+        w, b = exp[name]
+        total = total + (_master(layer, w) * dws[name].double()).sum() + (b * dbs[name][: layer.n_real].double()).sum()
+    want = torch.autograd.grad(total, cpu)
+    for prm, gg, w in zip(params, g0, want):
+        assert torch.allclose(prm.grad.double().cpu(), gg.double().cpu() + w, rtol=1e-6, atol=1e-6), prm.shape
+
+
+def test_shot_loss_step_batched_form_equals_grouped_form():
+    """sv_shot_loss_step (four equal groups of ONE batched launch, back to back in the order (1)(3)(2)(4)) re-points its
+    arguments onto sv_shot_loss_step2, which tests/test_model_gpu.py::test_fused_loss_node_equals_modular_criteria checks
+    against the modular criteria: the same twelve terms and gradients"""
+    from oracle import shotvae_oracle as O
+    from shot_vae_amd.steploss import shot_loss_step
+    B, D, K = 24, 128, 10
+    torch.manual_seed(19)
+    d = dev()
+    il, iu = torch.rand(B, 3, 32, 32, device=d), torch.rand(B, 3, 32, 32, device=d)
+    label = torch.randint(0, K, (B,), device=d)
+    perm_l, perm_u = torch.randperm(B, device=d), torch.randperm(B, device=d)
+    sch = O.schedule(37, dmi=2.3)
+    rec, mu = torch.randn(2 * B, 3, 32, 32, device=d), torch.randn(4 * B, D, device=d) * 0.5
+    ls, la = torch.randn(4 * B, D, device=d) * 0.3, torch.log_softmax(torch.randn(4 * B, K, device=d), 1)
+    t2, *g2 = shot_loss_step(rec, mu, ls, la, il, iu, label, perm_l, perm_u, 0.83, 0.37, sch)
+    a = L.SvShotLossArgs()
+    g1 = [torch.full_like(t, float("nan")) for t in (rec, mu, ls, la)]
+    t1 = torch.zeros(12, device=d)
+    scratch = torch.empty(10 + 4 * B * D + 2 * B * K, device=d)
+    a.rec, a.mu, a.ls, a.la = (t.data_ptr() for t in (rec, mu, ls, la))
+    a.d_rec, a.d_mu, a.d_ls, a.d_la = (t.data_ptr() for t in g1)
+    a.image_l, a.image_u, a.label_l, a.perm_l, a.perm_u = (t.data_ptr() for t in (il, iu, label, perm_l, perm_u))
+    a.lam_l, a.lam_u = 0.83, 0.37
+    a.B, a.D, a.K, a.bce, a.n_per_img, a.x_sigma = B, D, K, 1, il[0].numel(), 1.0
+    a.sch = L.SvShotSchedule(*[float(sch[k]) for k in ("ew", "kl_beta_c", "kl_beta_d", "cmi", "dmi", "pwm", "ucw")])
+    a.terms, a.coef, a.tgt = t1.data_ptr(), scratch.data_ptr(), scratch.data_ptr() + 40
+    L.call("sv_shot_loss_step", C.byref(a), st())
+    torch.cuda.synchronize()
+    assert rel(t1, t2) < 1e-6                       # (block sums meet through float atomics: last-bit order effects)
+    for x, y in zip(g1, g2):
+        assert not torch.isnan(x).any() and rel(x, y) < 1e-6
