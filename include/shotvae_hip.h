@@ -280,6 +280,38 @@ int sv_bn_bwd_apply(int dtype, int64_t M, int C, int ld, const void* x, const fl
                     const float* rstd, float count, const sv_bn_branch* br, int nbranch,
                     const void* residual, void* dx, int groups, void* stream);
 
+/* ---- dropout between conv1 and norm2 of a wide unit (wideresnet.py:23-36, nn.Dropout(drop_rate)) ----------------------------
+ * Masks are never stored: the forward and the backward regenerate them from a key, so nothing is saved and a captured graph
+ * stays valid.  The mask of element e -- its flat NHWC index inside ITS group's [B][H][W][C] tensor (the channel stride ld
+ * does not enter) -- is
+ *     r = word (e & 3) of Philox-4x32-10(counter = (q_lo, q_hi, unit, 0), key = (key_lo, key_hi)),  q = e >> 2
+ *     kept  <=>  r >= thr,     thr = (uint32)(p * 2^32) formed in double by the caller,   scale = (float)(1 / (1 - p))
+ *     out = kept ? round_to_dtype((float)x * scale) : 0          (round to nearest even; the same mask in both dtypes)
+ * key = keys[group] (an int64 in DEVICE memory, read by the kernels: a graph replays with whatever keys were drawn into it),
+ * unit = the 0-based index of the wide unit in the encoder.  Every entry point refuses (SV_E_ARG / SV_E_SHAPE, nothing
+ * launched): keys == NULL, p outside (0, 1), thr or scale inconsistent with p, C % 8 != 0.                                   */
+typedef struct {
+    const int64_t* keys;        /* [G]: the key of each group                                                                */
+    int32_t unit;
+    float p;
+    float scale;
+    uint32_t thr;
+} sv_dropout_args;
+/* out = dropout(x) (out may equal x: in place is the intended use) and, when stats != NULL, BatchNorm statistics of the STORED
+ * values: stats [G][R][2C] += (sum, sum of squares) -- the layout the conv epilogue fills (sv_igemm_args::stats), so that
+ * sv_bn_finalize / a folded consumer take them unchanged.  x / out [G][M][ld], M = rows of ONE group.  Block b adds to replica
+ * b % R; under SV_OPT_DETERMINISTIC the blocks store their partial sums to slots and a second pass adds them in index order
+ * (replica 0).                                                                                                               */
+int sv_dropout_fwd(int dtype, const void* x, int64_t M, int C, int ld, const sv_dropout_args* a, void* out, sv_acc_t* stats,
+                   int replicas, int groups, void* stream);
+/* sv_bn_bwd_apply of the BatchNorm behind a dropout, with the dropout's backward applied to its result:
+ * dx = kept ? dx_bn * scale : 0, rounded once.  residual must be NULL.                                                       */
+int sv_bn_bwd_apply_dropout(int dtype, int64_t M, int C, int ld, const void* x, const float* mean, const float* rstd, float count,
+                            const sv_bn_branch* br, int nbranch, const void* residual, void* dx, int groups,
+                            const sv_dropout_args* a, void* stream);
+/* the keep mask itself: out [G][M][C] bytes, 1 = kept (tests, tools; the step never materialises it)                        */
+int sv_dropout_mask(const int64_t* keys, int unit, uint32_t thr, int64_t M, int C, int groups, uint8_t* out, void* stream);
+
 /* out [B][H/2][W/2][C] = in [B][2y][2x][C]: the even positions of an NHWC tensor (C a multiple of 8)                      */
 int sv_gather_even(int dtype, const void* in, int B, int H, int W, int C, void* out, void* stream);
 

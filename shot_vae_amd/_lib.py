@@ -104,6 +104,20 @@ class SvBnBranch(C.Structure):
                 ("dbeta", C.c_void_p), ("replicas", C.c_int32), ("sparse", C.c_int32)]
 
 
+class SvDropoutArgs(C.Structure):
+    _fields_ = [("keys", C.c_void_p), ("unit", C.c_int32), ("p", C.c_float), ("scale", C.c_float), ("thr", C.c_uint32)]
+
+
+def dropout_args(keys_ptr, unit, p):
+    """sv_dropout_args for drop probability p (0 < p < 1): thr = (uint32)(p * 2^32) and scale = (float)(1 / (1 - p)), both
+    formed in double (the mask definition of include/shotvae_hip.h)"""
+    a = SvDropoutArgs()
+    a.keys, a.unit, a.p = keys_ptr, int(unit), float(p)
+    a.thr = int(float(p) * 4294967296.0)
+    a.scale = 1.0 / (1.0 - float(p))
+    return a
+
+
 P, I, I64, F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _PROTOS = {
     "sv_igemm": [C.POINTER(SvGeom), I, C.POINTER(SvIgemmArgs), P],
@@ -167,6 +181,9 @@ _PROTOS = {
     "sv_get_option": [I],
     "sv_bn_bwd_affine": [P, I, I, F, P, P, P, P, P, P, P, P, I, P],
     "sv_gather_even": [I, P, I, I, I, I, P, P],
+    "sv_dropout_fwd": [I, P, I64, I, I, C.POINTER(SvDropoutArgs), P, P, I, I, P],
+    "sv_bn_bwd_apply_dropout": [I, I64, I, I, P, P, P, F, C.POINTER(SvBnBranch), I, P, P, I, C.POINTER(SvDropoutArgs), P],
+    "sv_dropout_mask": [P, I, C.c_uint32, I64, I, I, P, P],
     "sv_stream_fork": [P, P, I],
     "sv_stream_flag_next": [P, P, P],
     "sv_stream_wait_flag": [P, P, C.c_uint32],
@@ -246,7 +263,8 @@ class options:
 # in-situ timing (bench.py): tag name -> id; every entry point is filed under its own name unless the engine filed the
 # launch under a per-layer tag first (Engine._tag, for sv_igemm / sv_wgrad)
 prof_tags = None
-_LAYER_TAGGED = ("sv_igemm", "sv_igemm_query_blocks", "sv_wgrad", "sv_wgrad_ex", "sv_bwd3x3", "sv_prof_tag", "sv_prof_enable", "sv_set_option")
+_LAYER_TAGGED = ("sv_igemm", "sv_igemm_query_blocks", "sv_wgrad", "sv_wgrad_ex", "sv_bwd3x3", "sv_dropout_fwd", "sv_prof_tag", "sv_prof_enable",
+                 "sv_set_option")
 
 
 def deterministic():

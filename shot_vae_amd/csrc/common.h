@@ -208,6 +208,40 @@ __device__ __forceinline__ void sv_bn_fold_block512(const sv_igemm_args& a, int 
     __syncthreads();
 }
 
+// ---- dropout mask (sv_dropout_fwd, sv_bn_bwd_apply_dropout, sv_dropout_mask; definition in shotvae_hip.h) -----------------
+// Philox-4x32-10 (Salmon et al., SC'11): ten rounds, the key bumped by the Weyl constants between rounds.
+struct sv_u32x4 { uint32_t v[4]; };
+__host__ __device__ __forceinline__ sv_u32x4 sv_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                              uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        if (r > 0) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t h0 = (uint32_t)(p0 >> 32), l0 = (uint32_t)p0, h1 = (uint32_t)(p1 >> 32), l1 = (uint32_t)p1;
+        c0 = h1 ^ c1 ^ k0;
+        c1 = l1;
+        c2 = h0 ^ c3 ^ k1;
+        c3 = l0;
+    }
+    return sv_u32x4{{c0, c1, c2, c3}};
+}
+// keep bits of the 8 elements e0 .. e0 + 7 (e0 % 8 == 0: two generator calls, counters q = e0 / 4 and q + 1); bit j = element e0 + j
+__device__ __forceinline__ uint32_t sv_dropout_keep8(uint64_t key, int unit, uint32_t thr, int64_t e0) {
+    const uint64_t q = (uint64_t)e0 >> 2;
+    const sv_u32x4 a = sv_philox4x32_10((uint32_t)q, (uint32_t)(q >> 32), (uint32_t)unit, 0u, (uint32_t)key, (uint32_t)(key >> 32));
+    const sv_u32x4 b = sv_philox4x32_10((uint32_t)(q + 1), (uint32_t)((q + 1) >> 32), (uint32_t)unit, 0u, (uint32_t)key,
+                                        (uint32_t)(key >> 32));
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        m |= (uint32_t)(a.v[j] >= thr) << j;
+        m |= (uint32_t)(b.v[j] >= thr) << (j + 4);
+    }
+    return m;
+}
+// the argument check every dropout entry point runs before it launches (keys, p in (0, 1), thr / scale consistent with p)
+int sv_dropout_check(const sv_dropout_args* a, const char* who);
+
 // Interleaved tile order of the one-block-per-CU kernels (bwd3x3f.hip, fwd3x3f.hip) for ANY grid size: at its step k a block takes tile
 // k * NC + slot of its group, and the blocks that share an XCD (the hardware deals blocks to the eight XCDs round-robin in linear
 // block-id order, x fastest) own CONSECUTIVE slots, so that vertically adjacent tiles -- which share halo rows -- meet in one L2.

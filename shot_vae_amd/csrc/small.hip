@@ -156,6 +156,7 @@ struct bnb_params {
 struct bnb_params_g {
     bnb_params g[SV_MAX_GROUPS];
     int det_groups;       // deterministic mode: > 0 = block (0, 0) alone adds dgamma / dbeta, the groups in index order
+    sv_dropout_args drop; // DROP (sv_bn_bwd_apply_dropout): the mask of the dropout in front of the BatchNorm; unread otherwise
 };
 // tensors [G][M][ld], mean / rstd [G][C], bsums [G][R][2C]
 static bnb_params_g bnb_expand(const bnb_params& p, int groups, int es) {
@@ -177,12 +178,15 @@ static bnb_params_g bnb_expand(const bnb_params& p, int groups, int es) {
         A.g[grp] = r;
     }
     A.det_groups = 0;
+    A.drop = sv_dropout_args{};
     return A;
 }
 
 // REG: (threads of the grid) % (C/8) == 0, so a thread always meets the same 8 channels and keeps their
 // coefficients [gamma*rstd, mean(g), mean(g*xhat)] (+ mean, rstd) in registers; otherwise they sit in LDS.
-template <typename T, bool REG>
+// DROP: x is the output of a dropout (sv_bn_bwd_apply_dropout): dx = kept ? dx * scale : 0 before the one rounding, the mask
+// regenerated from PG.drop (the element index of (m, c) is m * C + c inside the group, whatever ld is).  No residual.
+template <typename T, bool REG, bool DROP = false>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bnb_params_g PG) {
     typedef typename V8<T>::type V;
     const bnb_params& p = PG.g[blockIdx.y];        // batched launch: blockIdx.y = group (the host expanded the pointers)
@@ -327,6 +331,11 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bnb_params_g PG
             }
             if (R) acc += to_f(rv[j]);
             o[j] = acc;
+        }
+        if (DROP) {
+            const uint32_t keep = sv_dropout_keep8((uint64_t)PG.drop.keys[blockIdx.y], PG.drop.unit, PG.drop.thr, mm * p.C + cc);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] = ((keep >> j) & 1) ? o[j] * PG.drop.scale : 0.f;
         }
         V ov;
 #pragma unroll
@@ -1832,10 +1841,10 @@ static void det_collect(const float* part, int P, int n, int outer, double* out,
     hipLaunchKernelGGL((det_collect_kernel<double>), dim3((n + 255) / 256, outer), dim3(256), 0, s, part, P, n, out);
 }
 
-int sv_bn_bwd_apply(int dtype, int64_t M, int C, int ld, const void* x, const float* mean, const float* rstd,
-                    float count, const sv_bn_branch* br, int nbranch, const void* residual, void* dx,
-                    int groups, void* stream) {
-    SvProfScope prof_scope(stream);
+// sv_bn_bwd_apply / sv_bn_bwd_apply_dropout (drop != NULL: the DROP instantiations, checked by the caller)
+static int bn_bwd_apply_launch(int dtype, int64_t M, int C, int ld, const void* x, const float* mean, const float* rstd,
+                               float count, const sv_bn_branch* br, int nbranch, const void* residual, void* dx,
+                               int groups, const sv_dropout_args* drop, void* stream) {
     SV_REQUIRE(x && mean && rstd && br && dx && nbranch >= 1 && nbranch <= 2, SV_E_ARG, "sv_bn_bwd_apply: bad args");
     SV_REQUIRE(C % 8 == 0 && ld % 8 == 0, SV_E_SHAPE, "sv_bn_bwd_apply: C=%d ld=%d must be multiples of 8", C, ld);
     bnb_params p;
@@ -1898,9 +1907,23 @@ int sv_bn_bwd_apply(int dtype, int64_t M, int C, int ld, const void* x, const fl
         bnb_params_g A;
         DISPATCH_T(dtype, A = bnb_expand(p, groups, (int)sizeof(T)));
         A.det_groups = sv_deterministic() ? groups : 0;
+        if (drop) {
+            A.drop = *drop;
+            if (reg) DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true>), dim3(grid, groups), dim3(nthr), lds, (hipStream_t)stream, A));
+            else DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, true>), dim3(grid, groups), dim3(256), lds, (hipStream_t)stream, A));
+            return sv_check_launch("sv_bn_bwd_apply_dropout");
+        }
         if (reg) DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), dim3(grid, groups), dim3(nthr), lds, (hipStream_t)stream, A));
         else DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false>), dim3(grid, groups), dim3(256), lds, (hipStream_t)stream, A));
         return sv_check_launch("sv_bn_bwd_apply");
+    }
+    if (drop) {
+        bnb_params_g A;
+        DISPATCH_T(dtype, A = bnb_expand(p, groups, (int)sizeof(T)));
+        A.drop = *drop;
+        if (reg) DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true>), dim3(grid, groups), dim3(nthr), lds, (hipStream_t)stream, A));
+        else DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, true>), dim3(grid, groups), dim3(256), lds, (hipStream_t)stream, A));
+        return sv_check_launch("sv_bn_bwd_apply_dropout");
     }
     if (reg) {
         DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), dim3(grid, groups), dim3(nthr), lds, (hipStream_t)stream, bnb_expand(p, groups, (int)sizeof(T))));
@@ -1908,6 +1931,24 @@ int sv_bn_bwd_apply(int dtype, int64_t M, int C, int ld, const void* x, const fl
         DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false>), dim3(grid, groups), dim3(256), lds, (hipStream_t)stream, bnb_expand(p, groups, (int)sizeof(T))));
     }
     return sv_check_launch("sv_bn_bwd_apply");
+}
+
+int sv_bn_bwd_apply(int dtype, int64_t M, int C, int ld, const void* x, const float* mean, const float* rstd,
+                    float count, const sv_bn_branch* br, int nbranch, const void* residual, void* dx,
+                    int groups, void* stream) {
+    SvProfScope prof_scope(stream);
+    return bn_bwd_apply_launch(dtype, M, C, ld, x, mean, rstd, count, br, nbranch, residual, dx, groups, nullptr, stream);
+}
+
+int sv_bn_bwd_apply_dropout(int dtype, int64_t M, int C, int ld, const void* x, const float* mean, const float* rstd,
+                            float count, const sv_bn_branch* br, int nbranch, const void* residual, void* dx, int groups,
+                            const sv_dropout_args* a, void* stream) {
+    SvProfScope prof_scope(stream);
+    const int rc = sv_dropout_check(a, "sv_bn_bwd_apply_dropout");
+    if (rc) return rc;
+    SV_REQUIRE(!residual, SV_E_ARG, "sv_bn_bwd_apply_dropout: residual must be NULL (the dropout's BatchNorm has no skip input)");
+    SV_REQUIRE(C % 8 == 0, SV_E_SHAPE, "sv_bn_bwd_apply_dropout: C=%d must be a multiple of 8", C);
+    return bn_bwd_apply_launch(dtype, M, C, ld, x, mean, rstd, count, br, nbranch, residual, dx, groups, a, stream);
 }
 
 int sv_bn_bwd_affine(const double* bsums, int replicas, int C, float count, const float* gamma, const float* mean, const float* rstd,

@@ -105,13 +105,15 @@ class BNSpec:
 class Plan:
     """Architecture + memory layout (device independent)."""
 
-    def __init__(self, encoder_name, in_ch=3, img=32, ldc=128, K=10):
+    def __init__(self, encoder_name, in_ch=3, img=32, ldc=128, K=10, drop_rate=0.0):
         if "wideresnet" not in encoder_name:
             raise NotImplementedError("{} not implemented".format(encoder_name))
         if img != 32 or in_ch > CPAD:
             raise NotImplementedError("the MI355X path covers 32x32 inputs with <= 16 channels "
                                       "(BASELINE.json configs); got img=%s ch=%s" % (img, in_ch))
         self.name, self.in_ch, self.img, self.ldc, self.K = encoder_name, in_ch, img, ldc, K
+        # nn.Dropout(drop_rate) between conv1 and norm2 of every wide unit (wideresnet.py:23-36); 0 = none (no launch, no key)
+        self.drop_rate = float(drop_rate)
         _, width, n_units = parse_wideresnet(encoder_name)
         self.widths = [int(16 * width), int(32 * width), int(64 * width)]
         self.cfeat = self.widths[-1]
@@ -270,6 +272,7 @@ class Engine:
 
     def __init__(self, plan, compute_dtype="bf16"):
         self.plan = plan
+        self.drop_rate = plan.drop_rate
         self.set_compute_dtype(compute_dtype)
         p = plan
         self.param = torch.zeros(p.n_param, dtype=torch.float32)
@@ -675,6 +678,17 @@ class Engine:
         self._fused_since_fork = True
         L.call("sv_bwd3x3", C.byref(g), self.code, C.byref(a), self._stream())
 
+    def _dropout_fwd(self, c1, unit, keys, stats, replicas, groups):
+        """sv_dropout_fwd in place on conv1's output of wide unit `unit`, accumulating norm2's statistics (stats, replicas)"""
+        c = c1.shape[-1]
+        tag = "fwd:dropout_%d" % c
+        if self.prof_tags is not None:
+            L.lib().sv_prof_tag(self.prof_tags.setdefault(tag, len(self.prof_tags)))
+        self._cost(tag, 2 * c1.numel() * c1.element_size())          # read once, written once
+        a = L.dropout_args(keys.data_ptr(), unit, self.drop_rate)
+        L.call("sv_dropout_fwd", self.code, _vp(c1.data_ptr()), c1.numel() // c // groups, c, c, C.byref(a), _vp(c1.data_ptr()),
+               _vp(stats), replicas, groups, self._stream())
+
     # ------------------------------------------------------------------------------- forward
     def _bn_layout(self, G):
         """Offsets (in floats) of every BatchNorm's [scale | shift | mean | rstd] block in the per-forward scratch for G
@@ -688,7 +702,8 @@ class Engine:
             lay = self._bn_layouts[G] = (off, o)
         return lay
 
-    def forward(self, image, groups, eps, u, temperature, training, keep, rec_groups=None, update_order=None, x16=None):
+    def forward(self, image, groups, eps, u, temperature, training, keep, rec_groups=None, update_order=None, x16=None,
+                keys=None):
         """One BATCHED forward of G = len(groups) independent instances of the network that share the weights (the
         forwards (1)-(4) of a SHOT-VAE step, main_shot_vae.py:288,311,329,356, or a single one): every launch carries
         the G groups (sv_igemm_args::groups), each with its OWN BatchNorm batch statistics -- the reference's
@@ -706,10 +721,18 @@ class Engine:
         update_order  order[k] = the group of the reference's k-th forward (running-statistic updates; default group order)
         x16     optional: the NHWC16 image tensor (sv_nchw_to_nhwc of `image`) when the caller has already made it -- the
                 grouped step converts on its input-side stream, beside the previous step's backward
+        keys    dropout (drop_rate > 0, training only): int64 [G] device tensor, the mask key of each group (sv_dropout_args);
+                ignored in eval mode, where dropout is the identity
         Returns (rec NCHW fp32, mu, ls, la, ctx-or-None), all [G * B, ...]."""
         self._require_gpu(image)
         p = self.plan
         G = len(groups)
+        drop = training and self.drop_rate > 0
+        if drop:
+            if keys is None or not torch.is_tensor(keys) or keys.dtype != torch.int64 or keys.numel() != G or not keys.is_cuda:
+                raise ValueError("a training forward with drop_rate > 0 needs the dropout keys: an int64 device tensor of %d "
+                                 "(one per group)" % G)
+            keys = keys.contiguous()
         Bt = image.shape[0]
         assert Bt % G == 0, "the groups of a batched forward have equal batch sizes"
         B = Bt // G
@@ -812,8 +835,18 @@ class Engine:
             ho = h // un["stride"]
             c1 = torch.empty(Bt, ho, ho, un["cout"], dtype=T, device=dev)
             self._igemm(un["conv1"].geom_fwd(B), tin, pk + es * un["conv1"].fwd_off, c1, pro=pro1,
-                        stats=sptr("c1_%d" % i), tag="fwd:conv3x3_%dx%d_s%d" % (un["cin"], un["cout"], un["stride"]),
-                        groups=G)
+                        stats=None if drop else sptr("c1_%d" % i),
+                        tag="fwd:conv3x3_%dx%d_s%d" % (un["cin"], un["cout"], un["stride"]), groups=G)
+            if drop:
+                # dropout in place on c1, norm2's statistics of the STORED values: f.c1[i] is the dropped tensor, which is what
+                # conv2 (and its weight gradient) and norm2's backward read
+                if det:
+                    ds = torch.zeros(G * 2 * un["cout"], dtype=torch.float64, device=dev)
+                    det_stats["c1_%d" % i] = (ds, 1)
+                    sp, sr = ds.data_ptr(), 1
+                else:
+                    sp, sr = sbase + 8 * stat_off["c1_%d" % i], stat_rep["c1_%d" % i]
+                self._dropout_fwd(c1, i, keys, sp, sr, G)
             pro2 = finalize(un["bn2"], "c1_%d" % i, B * ho * ho, fold=True)
             tout = torch.empty(Bt, ho, ho, un["cout"], dtype=T, device=dev)
             if "convi" in un:
@@ -901,6 +934,7 @@ class Engine:
                 self.nbt += 1
         if not keep:
             return rec, mu, ls, la, None
+        f.drop_keys = keys if drop else None
         f.prot, f.feat, f.mu, f.ls, f.la = prot, feat, mu, ls, la
         f.eps, f.csoft, f.latent = eps, csoft, latent
         f.keep = (groups, u, stats)
@@ -1015,9 +1049,10 @@ class Engine:
                 return (raw, sc, sh, mn, rs, b.slope, alloc, None)
             return (raw, sc, sh, mn, rs, b.slope, bs_off[b.index], bs_rep[b.index])
 
-        def bn_apply(raw, branches, residual, count, Gx=None, sparse=(), compact=False):
+        def bn_apply(raw, branches, residual, count, Gx=None, sparse=(), compact=False, drop_unit=None):
             """branches: [(g tensor, BNSpec)] sharing `raw`; returns dL/d(raw) (+ residual).  count = rows of ONE group.
-            sparse: indices of branches whose g was written with sparse_out (defined at even positions only)."""
+            sparse: indices of branches whose g was written with sparse_out (defined at even positions only).
+            drop_unit: raw is the output of wide unit drop_unit's dropout -- the result is dL/d(the dropout's input)."""
             Gx = Gx or G
             arr = (L.SvBnBranch * len(branches))()
             for k, (g, b) in enumerate(branches):
@@ -1034,6 +1069,12 @@ class Engine:
             cc = raw.shape[-1]
             # reads x and one g per branch (+ the residual), writes dx
             # (a sparse branch is read at one position in four)
+            if drop_unit is not None:
+                self._cost("sv_bn_bwd_apply_dropout", raw.numel() * raw.element_size() * (2 + len(branches)))
+                da = L.dropout_args(f.drop_keys.data_ptr(), drop_unit, self.drop_rate)
+                L.call("sv_bn_bwd_apply_dropout", self.code, raw.numel() // cc // Gx, cc, cc, _vp(raw.data_ptr()), _vp(mn), _vp(rs),
+                       float(count), arr, len(branches), None, _vp(dx.data_ptr()), Gx, C.byref(da), st)
+                return dx
             self._cost("sv_bn_bwd_apply", raw.numel() * raw.element_size() *
                        (2 + len(branches) - 0.75 * len(sparse) + (residual is not None)))
             L.call("sv_bn_bwd_apply", self.code, raw.numel() // cc // Gx, cc, cc, _vp(raw.data_ptr()), _vp(mn), _vp(rs),
@@ -1174,7 +1215,11 @@ class Engine:
             cnt = tin.numel() // tin.shape[-1] // G
             g1 = torch.empty_like(tin)
             tag1 = "conv3x3_%dx%d_s%d" % (un["cin"], c, un["stride"])
-            if fb >= 1 and same:
+            # with dropout, c1 is the DROPPED tensor: conv2's backward above (fused, deferred boundary pass or pair) reads it only as
+            # conv2's input and as norm2's input, both right; conv1's fused backward would form dL/dc1 without the mask, so a unit
+            # with dropout takes the pair path, the mask applied in norm2's BatchNorm backward (sv_bn_bwd_apply_dropout)
+            drop_unit = i if f.drop_keys is not None else None
+            if fb >= 1 and same and drop_unit is None:
                 # conv1's WHOLE backward in one launch: dc1 = norm2's BatchNorm backward of g2 is formed in its load path from
                 # (g2, c1) and the finished sums (sv_bn_bwd_affine), both products run from that one LDS image
                 if self.fold_bn_bwd:
@@ -1187,7 +1232,7 @@ class Engine:
                 del lin21
                 dc1 = None
             else:
-                dc1 = bn_apply(c1, [(g2, un["bn2"])], None, cnt2)
+                dc1 = bn_apply(c1, [(g2, un["bn2"])], None, cnt2, drop_unit=drop_unit)
                 self._wgrad_async(un["conv1"].geom_fwd(B), tin, pro1, dc1, gbase + 4 * un["conv1"].master_off,
                                   tag="wgrad:" + tag1, groups=G, budget=pair1,
                                   then=lambda: self._igemm(un["conv1"].geom_dgrad(B), dc1, pk + es * un["conv1"].dgrad_off, g1,

@@ -117,6 +117,7 @@ def train_step_overlapped(model, elbo_criterion, cls_criterion, optimizer, image
     eng = model._engine
     eng.ensure_packs()
     model._attach_grads()
+    model.last_dropout_keys = []
     dl_l = dl_u = None
     if device_rng is not None:           # capturable: lambdas / pairings drawn on the device
         dl_l, dl_u = device_rng.next_lams()
@@ -234,6 +235,7 @@ def train_step_grouped(model, elbo_criterion, cls_criterion, optimizer, image_l,
     dev = image_l.device
     eng = model._engine
     launches = _launch_plan(Bl != Bu, optimal_match)
+    model.last_dropout_keys = []
     main = torch.cuda.current_stream() if image_l.is_cuda else None
     side_in = None
     if (input_stream and main is not None and len(launches) == 1 and not torch.cuda.is_current_stream_capturing()
@@ -274,20 +276,41 @@ def _grouped_inputs(model, image_l, label_l, image_u, epsilon, device_rng, optim
     eps, u = {}, {}
     perm_u = None
     device_noise = not (device_rng is None and model.rng == "host")
+    # dropout (training, drop_rate > 0): one key per forward, drawn in front of that forward's noise (the encoder runs before the
+    # sampler, vae.py:140-151) -- torch.randint, which the sampler's draws never use
+    drop = model._drop_active()
+    keys, keys_all = {}, None
     if not device_noise:
+        if drop:
+            keys[1] = torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)
         eps[1] = torch.randn(Bl, ldc)
         lam_l = np.random.beta(epsilon, epsilon) if epsilon > 0 else 1
         perm_l = torch.randperm(Bl).to(dev)
-        eps[2], eps[3], u[3] = torch.randn(Bl, ldc), torch.randn(Bu, ldc), torch.rand(Bu, K)
+        if drop:
+            keys[2] = torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)
+        eps[2] = torch.randn(Bl, ldc)
+        if drop:
+            keys[3] = torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)
+        eps[3], u[3] = torch.randn(Bu, ldc), torch.rand(Bu, K)
         lam_u = np.random.beta(2.0, 2.0)
         if not optimal_match:
             perm_u = torch.randperm(Bu).to(dev)
+        if drop:
+            keys[4] = torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64)
         eps[4], u[4] = torch.randn(Bu, ldc), torch.rand(Bu, K)
         for k in eps:
             eps[k] = eps[k].to(dev)
         for k in u:
             u[k] = u[k].to(dev)
+        for k in keys:
+            keys[k] = keys[k].to(dev)
     else:
+        if drop:
+            # the four keys in one draw on the device generator (capturable: every replay draws fresh ones), laid out like the
+            # noise below in the single launch's group order (1)(3)(2)(4)
+            keys_all = torch.randint(0, 2 ** 63 - 1, (4,), dtype=torch.int64, device=dev)
+            for j, k in enumerate((1, 3, 2, 4)):
+                keys[k] = keys_all[j:j + 1]
         e_all = torch.randn(2 * (Bl + Bu), ldc, device=dev)
         u_all = torch.rand(2 * (Bl + Bu), K, device=dev)
         o = 0
@@ -320,8 +343,9 @@ def _grouped_inputs(model, image_l, label_l, image_u, epsilon, device_rng, optim
             x16 = eng.to_nhwc16(image_cat)
     return dict(eps=eps, u=u, e_all=e_all, u_all=u_all, device_noise=device_noise, perm_l=perm_l, perm_u=perm_u, lam_l=lam_l,
                 lam_u=lam_u, sm_img=sm_img, sm_label=sm_label, images=images, specs=specs, mx_img=mx_img, image_cat=image_cat,
-                x16=x16, tensors=[e_all, u_all, perm_l, perm_u, sm_img, sm_label, mx_img, image_cat, x16, lam_l, lam_u] +
-                list(eps.values()) + list(u.values()))
+                x16=x16, keys=keys, keys_all=keys_all,
+                tensors=[e_all, u_all, perm_l, perm_u, sm_img, sm_label, mx_img, image_cat, x16, lam_l, lam_u, keys_all] +
+                list(eps.values()) + list(u.values()) + list(keys.values()))
 
 
 def _grouped_body(model, elbo_criterion, cls_criterion, optimizer, image_l, label_l, image_u, sch, distributed, label_u,
@@ -356,11 +380,13 @@ def _grouped_body(model, elbo_criterion, cls_criterion, optimizer, image_l, labe
             else:
                 zu = torch.zeros(B, K, device=dev) if zu is None else zu
                 us.append(zu)
+        keys = prep["keys"]
         if device_noise and len(launches) == 1:     # drawn in this launch's group order (uniform rows of label groups are unused)
-            e_cat, u_cat = e_all, u_all
+            e_cat, u_cat, k_cat = e_all, u_all, prep["keys_all"]
         else:
             e_cat = torch.cat([eps[k] for k in ids]) if len(ids) > 1 else eps[ids[0]]
             u_cat = torch.cat(us) if len(ids) > 1 else us[0]
+            k_cat = (torch.cat([keys[k] for k in ids]) if len(ids) > 1 else keys[ids[0]]) if keys else None
         nrec = sum(1 for k in ids if k in (1, 3))
         order = sorted(range(len(ids)), key=lambda j: ids[j])                # running statistics: the reference's forward order
         if len(launches) > 1:
@@ -370,7 +396,8 @@ def _grouped_body(model, elbo_criterion, cls_criterion, optimizer, image_l, labe
                 rec, mu, ls, la, fctx = model.forward_groups_direct([images[k] for k in ids], [specs[k] for k in ids], eps=e_cat,
                                                                     u=u_cat, rec_groups=nrec, update_order=order,
                                                                     image_cat=prep["image_cat"] if len(launches) == 1 else None,
-                                                                    x16=prep["x16"] if len(launches) == 1 else None)
+                                                                    x16=prep["x16"] if len(launches) == 1 else None,
+                                                                    keys=k_cat)
         finally:
             eng.defer_slot = None
         ctxs.append((ids, fctx, rec, mu, ls, la))
@@ -425,6 +452,7 @@ def train_step(model, elbo_criterion, cls_criterion, optimizer, image_l, label_l
     compare against the oracle."""
     K = model._plan.K
     Bl, Bu = image_l.size(0), image_u.size(0)
+    model.last_dropout_keys = []
     onehot_l = one_hot(label_l, K)
     # (1) labelled forward                                                   :288-295
     rec1, mu1, ls1, la1 = model(image_l, disc_label=label_l)
@@ -486,6 +514,7 @@ def m2_train_step(model, elbo_criterion, cls_criterion, optimizer, image_l, labe
     Also returns the monitored KL(q(y|x) || smoothed label) of :285-291."""
     K = model._plan.K
     B = image_l.size(0)
+    model.last_dropout_keys = []
     onehot_l = one_hot(label_l, K)
     rec1, mu1, ls1, la1 = model(image_l, disc_label=label_l)
     recon_l, klc_l, kld_l = elbo_criterion(image_l, rec1, mu1, ls1, la1)

@@ -8,8 +8,13 @@ the loop of main_shot_vae.py:261-383 runs unchanged.  Differences (all documente
     all-reduce of the flat gradient buffer (see dp.py), not nn.DataParallel;
   * gradients of the parameters are accumulated by the kernels straight into one flat fp32 buffer
     (``p.grad`` are views of it);
-  * only the wideresnet encoders on 32x32 inputs are implemented (the BASELINE.json configs).
+  * only the wideresnet encoders on 32x32 inputs are implemented (the BASELINE.json configs);
+  * dropout (``drop_rate``) draws one int64 key per training forward (torch.randint, in front of that forward's
+    noise) and regenerates its masks from it in the kernels (shotvae_hip.h, sv_dropout_args): the masks differ from
+    torch's nn.Dropout draws, their distribution does not.
 """
+import math
+
 import torch
 from torch import nn
 
@@ -42,10 +47,10 @@ class _VAEFunction(torch.autograd.Function):
     hand-written HIP backward."""
 
     @staticmethod
-    def forward(ctx, anchor, model, image, groups, eps, u, rec_groups=None, update_order=None):
+    def forward(ctx, anchor, model, image, groups, eps, u, rec_groups=None, update_order=None, keys=None):
         eng = model._engine
         rec, mu, ls, la, f = eng.forward(image, groups, eps, u, model._temperature, model.training, keep=True,
-                                         rec_groups=rec_groups, update_order=update_order)
+                                         rec_groups=rec_groups, update_order=update_order, keys=keys)
         ctx.model, ctx.f = model, f
         # an output that enters no loss term arrives as None in backward (not as a zero tensor): the reconstruction of
         # the mixed forwards (main_shot_vae.py:311,356) -- their decoder backward is then skipped, as autograd does in the
@@ -67,7 +72,7 @@ class _VAEFunction(torch.autograd.Function):
         model._attach_grads()
         eng = model._engine
         eng.backward(f, d_rec.contiguous().float() if d_rec is not None else None, d_mu, d_ls, d_la)
-        return (None,) * 8
+        return (None,) * 9
 
 
 class VariationalAutoEncoder(nn.Module):
@@ -79,21 +84,30 @@ class VariationalAutoEncoder(nn.Module):
             # densenet / preactresnet encoders exist in the reference (vae.py:93-104) but are outside
             # every BASELINE.json config; same error type as the reference's fall-through (vae.py:106)
             raise NotImplementedError("{} not implemented".format(encoder_name))
-        if drop_rate != 0:
-            raise NotImplementedError("drop_rate != 0 is not implemented (main_shot_vae.py:60 default is 0)")
+        drop_rate = float(drop_rate)
+        if math.isnan(drop_rate) or drop_rate < 0 or drop_rate > 1:
+            raise ValueError("dropout probability has to be between 0 and 1, but got {}".format(drop_rate))
+        if drop_rate == 1:
+            raise NotImplementedError("drop_rate == 1 is not supported: the whole tensor into norm2 would be zero, and its "
+                                      "BatchNorm has no batch statistics to normalise with")
         if not small_input:
             raise NotImplementedError("small_input=False (7x7 stem + max-pool) is not implemented; the "
                                       "CIFAR/SVHN configs of main_shot_vae.py use small_input=True")
         if tuple(img_size) != (32, 32):
             raise NotImplementedError("only 32x32 inputs are implemented")
         plan = Plan(encoder_name, in_ch=num_input_channels, img=img_size[0], ldc=continuous_latent_dim,
-                    K=int(disc_latent_dim))
+                    K=int(disc_latent_dim), drop_rate=drop_rate)
         self._plan = plan
         self._engine = Engine(plan, compute_dtype)
         self._temperature = sample_temperature
         self._data_parallel = data_parallel
         self._disc_latent_dim = disc_latent_dim
         self.rng = rng
+        self.drop_rate = drop_rate
+        # debugging aid: the int64 [G] dropout-key tensor of every training forward with drop_rate > 0, in call order (the
+        # step functions clear it when they start; at most the last 16 are kept).  With these, a test regenerates each
+        # forward's masks (sv_dropout_mask).
+        self.last_dropout_keys = []
         self._views = []          # (parameter, flat offset/spec) for re-pointing after device moves
         self._engine.init_default()
         self._build_tree()
@@ -199,16 +213,32 @@ class VariationalAutoEncoder(nn.Module):
         """(param, grad) flat fp32 buffers: what FlatSGD updates and dp.all_reduce reduces."""
         return self._engine.param, self._engine.grad
 
+    def _drop_active(self):
+        return self.training and self.drop_rate > 0
+
+    def _draw_keys(self, n, dev):
+        """n dropout keys (int64, on dev): host RNG -> the CPU generator and a copy, device RNG -> the device generator.
+        torch.randint, never randn / rand: those carry the sampler's noise."""
+        if self.rng == "host":
+            return torch.randint(0, 2 ** 63 - 1, (n,), dtype=torch.int64).to(dev)
+        return torch.randint(0, 2 ** 63 - 1, (n,), dtype=torch.int64, device=dev)
+
+    def _log_keys(self, keys):
+        self.last_dropout_keys.append(keys)
+        del self.last_dropout_keys[:-16]
+
     def _draw_noise(self, B, dev, gumbel):
-        """noise in the reference's order: randn for z (vae.py:37,82), then rand for gumbel (vae.py:52,69)"""
+        """noise in the reference's order: randn for z (vae.py:37,82), then rand for gumbel (vae.py:52,69).  With dropout in
+        training mode the forward's key comes first (the encoder runs before the sampler, vae.py:140-151): (eps, u, key)"""
         plan = self._plan
+        key = self._draw_keys(1, dev) if self._drop_active() else None
         if self.rng == "host":
             eps = torch.randn(B, plan.ldc).to(dev)
             u = torch.rand(B, plan.K).to(dev) if gumbel else None
         else:
             eps = torch.randn(B, plan.ldc, device=dev)
             u = torch.rand(B, plan.K, device=dev) if gumbel else None
-        return eps, u
+        return eps, u, key
 
     @staticmethod
     def _group_spec(mixup, disc_label, disc_pseudo_label, mixup_lam):
@@ -225,10 +255,10 @@ class VariationalAutoEncoder(nn.Module):
         if not input_img.is_cuda:
             raise L.ShotVaeHipError("VariationalAutoEncoder: input is not on an MI355X (no CPU fallback)")
         spec = self._group_spec(mixup, disc_label, disc_pseudo_label, mixup_lam)
-        eps, u = self._draw_noise(input_img.size(0), input_img.device, spec[0] == 0)
-        return self._run(input_img, [spec], eps, u)
+        eps, u, key = self._draw_noise(input_img.size(0), input_img.device, spec[0] == 0)
+        return self._run(input_img, [spec], eps, u, keys=key)
 
-    def forward_groups(self, images, specs, eps=None, u=None, rec_groups=None, update_order=None):
+    def forward_groups(self, images, specs, eps=None, u=None, rec_groups=None, update_order=None, keys=None):
         """Several forward calls as ONE batched launch sequence (extension; see Engine.forward): images = list of equally
         sized batches, specs = list of dicts with the keyword arguments of forward() (mixup, disc_label,
         disc_pseudo_label, mixup_lam).  Equivalent to calling forward() on each batch -- every group keeps its own
@@ -237,7 +267,8 @@ class VariationalAutoEncoder(nn.Module):
         group in the reference's order.  rec_groups = Gd: only the first Gd batches' reconstructions are produced and
         differentiated (the others' last ConvTranspose and decoder backward are skipped; reconstruction is [Gd * B, ...]);
         update_order[k] = the list position of the reference's k-th forward (order of the BatchNorm running-statistic
-        updates; default list order).  Returns the 4-tuple of forward() with the groups concatenated along dim 0."""
+        updates; default list order).  keys: the dropout keys (int64 [G] on the device; drop_rate > 0 in training mode only),
+        drawn here if None.  Returns the 4-tuple of forward() with the groups concatenated along dim 0."""
         G = len(images)
         B = images[0].size(0)
         if any(im.size(0) != B for im in images):
@@ -247,23 +278,32 @@ class VariationalAutoEncoder(nn.Module):
                                sp.get("mixup_lam")) for sp in specs]
         if eps is None:
             pairs = [self._draw_noise(B, dev, g[0] == 0) for g in gs]
-            eps = torch.cat([e for e, _ in pairs])
-            if any(uu is not None for _, uu in pairs):
+            eps = torch.cat([e for e, _, _ in pairs])
+            if any(uu is not None for _, uu, _ in pairs):
                 z = torch.zeros(B, self._plan.K, device=dev)
-                u = torch.cat([uu if uu is not None else z for _, uu in pairs])
-        return self._run(torch.cat([im.float() for im in images]), gs, eps, u, rec_groups, update_order)
+                u = torch.cat([uu if uu is not None else z for _, uu, _ in pairs])
+            if keys is None and self._drop_active():
+                keys = torch.cat([k for _, _, k in pairs])
+        if keys is None and self._drop_active():
+            keys = self._draw_keys(G, dev)
+        return self._run(torch.cat([im.float() for im in images]), gs, eps, u, rec_groups, update_order, keys)
 
-    def forward_groups_direct(self, images, specs, eps, u, rec_groups=None, update_order=None, image_cat=None, x16=None):
+    def forward_groups_direct(self, images, specs, eps, u, rec_groups=None, update_order=None, image_cat=None, x16=None,
+                              keys=None):
         """forward_groups for a caller that runs the backward itself (no autograd node): returns (rec, mu, ls, la, ctx); pass
         ctx and the gradients w.r.t. the four outputs to backward_direct().  image_cat / x16: the concatenated images and
-        their NHWC16 form when the caller has already made them (train_step_grouped's input-side stream)."""
+        their NHWC16 form when the caller has already made them (train_step_grouped's input-side stream).  keys: the dropout
+        keys (int64 [G] on the device), required in training mode with drop_rate > 0."""
         gs = [self._group_spec(sp.get("mixup", False), sp.get("disc_label"), sp.get("disc_pseudo_label"),
                                sp.get("mixup_lam")) for sp in specs]
         with torch.no_grad():
             if image_cat is None:
                 image_cat = torch.cat([im.float() for im in images])
+            if self._drop_active():
+                self._log_keys(keys)
             return self._engine.forward(image_cat, gs, eps, u, self._temperature, self.training, keep=True,
-                                        rec_groups=rec_groups, update_order=update_order, x16=x16)
+                                        rec_groups=rec_groups, update_order=update_order, x16=x16,
+                                        keys=keys if self._drop_active() else None)
 
     def backward_direct(self, ctx, d_rec, d_mu, d_ls, d_la, own_grads=False):
         """accumulates the parameter gradients of a forward_groups_direct() call into the flat gradient buffer (p.grad).
@@ -274,13 +314,17 @@ class VariationalAutoEncoder(nn.Module):
         with torch.no_grad():
             self._engine.backward(ctx, d_rec, d_mu, d_ls, d_la, own_grads)
 
-    def _run(self, image, groups, eps, u, rec_groups=None, update_order=None):
+    def _run(self, image, groups, eps, u, rec_groups=None, update_order=None, keys=None):
         eng = self._engine
         dev = image.device
+        if not self._drop_active():
+            keys = None
+        elif keys is not None:
+            self._log_keys(keys)
         if torch.is_grad_enabled():
             if self._anchor is None or self._anchor.device != dev:
                 self._anchor = torch.zeros(1, device=dev, requires_grad=True)
-            return _VAEFunction.apply(self._anchor, self, image, groups, eps, u, rec_groups, update_order)
+            return _VAEFunction.apply(self._anchor, self, image, groups, eps, u, rec_groups, update_order, keys)
         rec, mu, ls, la, _ = eng.forward(image, groups, eps, u, self._temperature, self.training, keep=False,
-                                         rec_groups=rec_groups, update_order=update_order)
+                                         rec_groups=rec_groups, update_order=update_order, keys=keys)
         return rec, mu, ls, la
