@@ -604,12 +604,15 @@ int sv_debug_conv_chunk_program(int* items, int* waits);
  *     capture), the second adds the slots in index order; the head weight gradient one slice after the other; BatchNorm
  *     dgamma / dbeta of a batched launch by one block, the groups in index order.
  * Default 0.
- * SV_OPT_ENABLE_MASK: OR of SV_K_* bits of kernels that are OFF by default (none at present: the 64 x 64-block narrow weight
- * gradient of round 4 lost to the 64 x 32 form inside the step twice and left the tree).                                      */
+ * SV_OPT_ENABLE_MASK: OR of SV_K_* bits of kernels that are OFF by default (SV_K_MAP4_CONV: the chunked conv3x3 kernel on 4 x 4 maps,
+ * which did not beat the gather-GEMM on the 512 -> 512 layers of the PreActResNets).                                      */
 enum { SV_OPT_DISABLE_MASK = 0, SV_OPT_WIDE_MIN_BLOCKS = 1, SV_OPT_HALO_ALL = 2, SV_OPT_PERSISTENT_BLOCKS = 3,
        SV_OPT_DETERMINISTIC = 4, SV_OPT_ENABLE_MASK = 5 };
 enum { SV_K_CONV3X3 = 1, SV_K_CONV3X3P = 2, SV_K_CONV3X3M = 4, SV_K_CONV3X3W = 8, SV_K_CONV3X3X = 16,
-       SV_K_WGRAD3X3 = 32, SV_K_WGRAD3X3W = 64, SV_K_IGEMM_KV2 = 128, SV_K_HALO = 256, SV_K_HALOP = 512, SV_K_HWGRAD = 1024, SV_K_IGEMM_BIG = 2048, SV_K_WGRAD_WIDE = 4096, SV_K_IGEMM_ALIGNED = 8192, SV_K_IGEMM_DMA = 16384, SV_K_WGRAD_INCR = 32768, SV_K_WGRAD3X3M = 65536, SV_K_TCONVR = 131072, SV_K_TCONVR_EX = 262144, SV_K_SCONV = 524288, SV_K_PCONV = 8388608, SV_K_THCONV = 16777216, SV_K_THWGRAD = 67108864, SV_K_S2WGRAD = 134217728 };
+       SV_K_WGRAD3X3 = 32, SV_K_WGRAD3X3W = 64, SV_K_IGEMM_KV2 = 128, SV_K_HALO = 256, SV_K_HALOP = 512, SV_K_HWGRAD = 1024, SV_K_IGEMM_BIG = 2048, SV_K_WGRAD_WIDE = 4096, SV_K_IGEMM_ALIGNED = 8192, SV_K_IGEMM_DMA = 16384, SV_K_WGRAD_INCR = 32768, SV_K_WGRAD3X3M = 65536, SV_K_TCONVR = 131072, SV_K_TCONVR_EX = 262144, SV_K_SCONV = 524288, SV_K_PCONV = 8388608, SV_K_THCONV = 16777216, SV_K_THWGRAD = 67108864, SV_K_S2WGRAD = 134217728,
+       SV_K_MAP4 = 268435456,      /* wgrad3x3 on 4 x 4 maps (ON by default: 236 against 405 us at 512 -> 512, 4 x 512 images) */
+       SV_K_MAP4_CONV = 536870912  /* conv3x3 (forward / data gradient) on 4 x 4 maps: OFF by default (SV_OPT_ENABLE_MASK) -- measured
+                                      224 against 235 us forward (inside the run-to-run spread), 191 against 161 us data gradient */ };
 int sv_set_option(int key, int value);
 int sv_get_option(int key);          /* -1 for an unknown key */
 

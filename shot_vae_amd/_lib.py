@@ -196,6 +196,8 @@ OPT_DISABLE_MASK, OPT_WIDE_MIN_BLOCKS, OPT_HALO_ALL, OPT_PERSISTENT_BLOCKS, OPT_
  K_WGRAD_WIDE, K_IGEMM_ALIGNED, K_IGEMM_DMA, K_WGRAD_INCR, K_WGRAD3X3M, K_TCONVR, K_TCONVR_EX, K_SCONV) = (1 << i for i in range(20))
 # (bits 20-22 and 25 belonged to experiments -- cconv / swgrad / the thconv forward forms / fwd3x3f: tools/experiments/)
 K_PCONV, K_THCONV, K_THWGRAD, K_S2WGRAD = 1 << 23, 1 << 24, 1 << 26, 1 << 27
+K_MAP4 = 1 << 28           # wgrad3x3 on 4 x 4 maps (the last stage of the PreActResNets); on by default (disable mask)
+K_MAP4_CONV = 1 << 29      # conv3x3 forward / data gradient on 4 x 4 maps; OFF by default (enable mask): it did not beat the gather-GEMM
 EXPORTS = sorted(list(_PROTOS) + ["sv_last_error"])
 
 _lib = None

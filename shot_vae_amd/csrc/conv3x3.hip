@@ -853,7 +853,8 @@ int launch_w(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
 static bool conv3x3_covers(const sv_geom* g) {
     if (g->nphase != 1 || g->phase[0].ntap != 9 || g->sy != 1 || g->sx != 1 || g->osy != 1 || g->osx != 1) return false;
     if (g->Hq != g->Hin || g->Wq != g->Win || g->Hout != g->Hin || g->Wout != g->Win || g->Hin != g->Win) return false;
-    if (g->Win != 8 && g->Win != 16 && g->Win != 32) return false;
+    if (g->Win != 4 && g->Win != 8 && g->Win != 16 && g->Win != 32) return false;
+    if (g->Win == 4 && !sv_enabled(SV_K_MAP4_CONV)) return false;      // OFF by default: see sv_conv3x3_try
     if (g->Cin % CK != 0 || g->ldx != g->Cin || g->N % 32 != 0) return false;
     if (g->phase[0].ooy != 0 || g->phase[0].oox != 0) return false;
     for (int t = 0; t < 9; ++t)
@@ -864,6 +865,19 @@ static bool conv3x3_covers(const sv_geom* g) {
 int sv_conv3x3_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc) {
     if (!conv3x3_covers(g)) return 0;
     const int TR = 128 / g->Win;
+    if (g->Win == 4) {
+        // 4 x 4 maps (the last stage of the PreActResNets, 512 -> 512): a 128-pixel tile is EIGHT whole images.  The chunked kernel
+        // stages the tile's 32 + 2 global rows as they lie in memory and masks, per lane, the taps that would cross an image's
+        // first / last row (yrow), so the neighbour image's rows in the halo are never multiplied.  Batches with B % 8 != 0 were
+        // refused by conv3x3_covers and stay with the gather-GEMM.
+        // NOT dispatched by default (SV_OPT_ENABLE_MASK, SV_K_MAP4_CONV): at 512 -> 512 and 4 x 512 images the forward took 224 us
+        // (209 .. 257) against the gather-GEMM's 235 (230 .. 239) -- a margin inside the spread -- and the data gradient 191 against
+        // 161 us (the prologue-free gather-GEMM stages both operands by LDS-DMA).  Every block re-reads the whole 64 x 9 x 512 weight
+        // slice for 128 pixels; a tile of 256+ pixels would halve that.  Kept reachable for the tests and the next attempt.
+        if (dtype == SV_BF16) *rc = g->N % 64 == 0 ? launch<bf16, 4, 2>(g, a, s) : launch<bf16, 2, 2>(g, a, s);
+        else *rc = launch<float, 2, 2>(g, a, s);
+        return 1;
+    }
     const bool no_persist = sv_disabled(SV_K_CONV3X3P);
     if (!no_persist && dtype == SV_BF16 && (g->Cin == 32 || g->Cin == 64)) {
         // whole weight slab resident in LDS: persistent software-pipelined kernel

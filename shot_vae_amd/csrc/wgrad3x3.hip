@@ -50,11 +50,13 @@ struct wg3_params {
 
 // 8 consecutive pixels (k = 8g + j) of one (shifted) image row, 16 channels starting at col0: k-major
 // fragment through the transposing read.  pix_elem_q = element offset of pixel 8g+q, q = (lane&15)>>2.
-__device__ __forceinline__ bf16x8 frag_tr(const bf16* S, int pix_elem_q, int col0, int lane) {
+// hi_elem = element offset of pixel 8g+4+q from pixel 8g+q: 4 * LDH inside one row; on 4-pixel-wide maps that pixel is the same
+// column of the NEXT image row (8g is even-row aligned, so both rows belong to one image): one LDS halo row further.
+__device__ __forceinline__ bf16x8 frag_tr(const bf16* S, int pix_elem_q, int col0, int lane, int hi_elem = 4 * LDH) {
     typedef __attribute__((address_space(3))) s16x4 lds_v4;
     const bf16* a0 = S + pix_elem_q + col0 + 4 * (lane & 3);
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(a0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(a0 + 4 * LDH));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(a0 + hi_elem));
     union { s16x4 s[2]; bf16x8 b; } u;
     u.s[0] = lo;
     u.s[1] = hi;
@@ -208,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3_kernel(const sv_geom g, const
                 const int hbase = ((jrow + 1 + jrow / HH) * WP + xcol + 1) * LDH;
 #pragma unroll
                 for (int t = 0; t < 9; ++t)
-                    F.fx[t] = frag_tr(Hb, hbase + (tap_off(pdy, t) * WP + tap_off(pdx, t)) * LDH, 16 * wj, lane);
+                    F.fx[t] = frag_tr(Hb, hbase + (tap_off(pdy, t) * WP + tap_off(pdx, t)) * LDH, 16 * wj, lane, (W >= 8 ? 4 : WP) * LDH);
             };
             auto mma_frags = [&](const Frags& F) {
 #pragma unroll
@@ -1080,6 +1082,15 @@ int launch(const sv_geom* g, const wg3_params& p, hipStream_t s) {
     const int grid = p.splits * nNC;
     constexpr int HHn = (TR < W) ? TR : W, LROWSn = TR + TR / HHn + 1;
     const size_t lds = (size_t)(128 + LROWSn * (W + 2)) * LDH * sizeof(T);
+    // fp32 on 4 x 4 maps (eight spacer rows): 70 KiB of dynamic LDS needs the opt-in -- the first launch of this family that does.
+    // One flag per instantiation, as in conv3x3.hip: like the dispatcher options it assumes one device and no concurrent first calls.
+    static bool optin = false;
+    if (lds > 64 * 1024 && !optin) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_kernel<T, WLOG, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_kernel<T, WLOG, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return sv_check_launch("hipFuncSetAttribute(wgrad3x3)");
+        optin = true;
+    }
     sv_prof_begin(s);
     if (sizeof(T) == 2 && g->N * g->Cin <= 64 * 64)
         hipLaunchKernelGGL((wgrad3x3_kernel<T, WLOG, 2>), dim3(grid, p.groups), dim3(256), lds, s, *g, sv_expand_wg(*g, p, p.groups, (int)sizeof(T)));
@@ -1154,7 +1165,8 @@ int sv_wgrad3x3_try(const sv_geom* g, int dtype, const void* x, const float* pro
                     int* rc) {
     if (g->nphase != 1 || g->phase[0].ntap != 9 || g->sy != 1 || g->sx != 1 || g->osy != 1 || g->osx != 1) return 0;
     if (g->Hq != g->Hin || g->Wq != g->Win || g->Hout != g->Hin || g->Wout != g->Win || g->Hin != g->Win) return 0;
-    if (g->Win != 8 && g->Win != 16 && g->Win != 32) return 0;
+    if (g->Win != 4 && g->Win != 8 && g->Win != 16 && g->Win != 32) return 0;
+    if (g->Win == 4 && sv_disabled(SV_K_MAP4)) return 0;
     if (g->Cin % 32 != 0 || g->N % 32 != 0 || g->ldx != g->Cin || g->ldo != g->N) return 0;
     if (g->phase[0].ooy != 0 || g->phase[0].oox != 0) return 0;
     for (int t = 0; t < 9; ++t)
@@ -1166,7 +1178,7 @@ int sv_wgrad3x3_try(const sv_geom* g, int dtype, const void* x, const float* pro
     p.unit = 0;
     p.groups = groups;
     const int nT = g->B * g->Hin / TR;          // per group
-    if (!sv_disabled(SV_K_WGRAD3X3W) && dtype == SV_BF16 && g->N % 160 == 0 && g->Cin >= 96) {
+    if (g->Win != 4 && !sv_disabled(SV_K_WGRAD3X3W) && dtype == SV_BF16 && g->N % 160 == 0 && g->Cin >= 96) {
         // wide layers: 160 x 32 slabs, one block (one wave per SIMD) per CU.  Pick the split count and the affinity unit
         // (a divisor of the chunk count) that minimise the modelled time:
         //   compute: rounds-of-32-CUs-per-XCD x (tiles per block + publishing a 160 x 32 x 9 slab, ~4 tiles) x 2.0 us
@@ -1214,7 +1226,8 @@ int sv_wgrad3x3_try(const sv_geom* g, int dtype, const void* x, const float* pro
         return 1;
     }
     // bf16: the 32x32x16 kernel with 64- (or 32-) channel n tiles
-    const bool use_m = dtype == SV_BF16 && !sv_disabled(SV_K_WGRAD3X3M);
+    // (4 x 4 maps -- eight whole images per tile, zero spacer rows between them in LDS -- take the 32 x 32-slab kernel only)
+    const bool use_m = dtype == SV_BF16 && !sv_disabled(SV_K_WGRAD3X3M) && g->Win != 4;
     const int NBm = use_m && g->N % 64 == 0 ? 64 : 32;
     const int nNC = (g->N / NBm) * (g->Cin / 32);
     // ~two persistent blocks per CU; every block should still see a few tiles
@@ -1241,6 +1254,7 @@ int sv_wgrad3x3_try(const sv_geom* g, int dtype, const void* x, const float* pro
     switch (g->Win) {
         case 32: *rc = dtype == SV_BF16 ? launch<bf16, 5>(g, p, s) : launch<float, 5>(g, p, s); break;
         case 16: *rc = dtype == SV_BF16 ? launch<bf16, 4>(g, p, s) : launch<float, 4>(g, p, s); break;
+        case 4: *rc = dtype == SV_BF16 ? launch<bf16, 2>(g, p, s) : launch<float, 2>(g, p, s); break;
         default: *rc = dtype == SV_BF16 ? launch<bf16, 3>(g, p, s) : launch<float, 3>(g, p, s); break;
     }
     return 1;

@@ -2,7 +2,8 @@
 weight shadows, and the launch sequences of one forward and one backward over the C ABI
 (include/shotvae_hip.h).  PyTorch is used for device memory and streams only.
 
-Reference being replaced: shot_vae_model/wideresnet.py:8-114 (encoder), shot_vae_model/decoder.py:4-69,
+Reference being replaced: shot_vae_model/wideresnet.py:8-114 and shot_vae_model/preactresnet.py:4-133 (basic units: 18 / 34)
+(encoders), shot_vae_model/decoder.py:4-69,
 shot_vae_model/vae.py:10-151 (heads, sampler, assembly) and autograd's backward of those.
 
 Data layout in HBM
@@ -44,6 +45,32 @@ def parse_wideresnet(name):
     depth, width = int(depth), int(width)
     assert (depth - 4) % 6 == 0, "depth should be 6n+4"
     return depth, width, (depth - 4) // 6
+
+
+# preactresnet.py:120-126: name -> (expansion, units per stage)
+PREACT_CONFIGS = {"preactresnet18": (1, [2, 2, 2, 2]), "preactresnet34": (1, [3, 4, 6, 3]), "preactresnet50": (4, [3, 4, 6, 3]),
+                  "preactresnet101": (4, [3, 4, 23, 3]), "preactresnet152": (4, [3, 8, 36, 3])}
+
+
+def encoder_family(name):
+    """The encoder family of `name` as the plan needs it: dict(stem = stem width, widths = channels per stage, units = units per
+    stage, slope = activation slope of the body BatchNorms and the transition, slope_i = ... of a shortcut's BatchNorm (1.0: none),
+    block / unit = state_dict key formats of stage s and unit u, both from 1).  Errors mirror the reference's (vae.py:93-106)."""
+    if "densenet" in name:
+        raise NotImplementedError("{} not implemented (DenseNet encoders are not built: DESIGN.md section 7)".format(name))
+    if "wideresnet" in name:
+        _, width, n_units = parse_wideresnet(name)
+        return dict(stem=16, widths=[int(16 * width), int(32 * width), int(64 * width)], units=[n_units] * 3,
+                    slope=LEAKY_SLOPE, slope_i=LEAKY_SLOPE, block="wideblock%d.wide_block.", unit="wideunit%d.")
+    if "preactresnet" in name:
+        expansion, units = PREACT_CONFIGS[name]           # KeyError for an unknown name, as preactresnet.py:131
+        if expansion != 1:
+            raise NotImplementedError("{} not implemented: the bottleneck PreActResNets (50 / 101 / 152: three convolutions and "
+                                      "three BatchNorms per unit) are not built; preactresnet18 / preactresnet34 are".format(name))
+        # preactresnet.py:19-65: ReLU instead of LeakyReLU, and the shortcut's BatchNorm has NO activation (its ReLU is commented out)
+        return dict(stem=64, widths=[64, 128, 256, 512], units=list(units), slope=0.0, slope_i=1.0,
+                    block="block%d.preact_block.", unit="unit%d.")
+    raise NotImplementedError("{} not implemented".format(name))
 
 
 class ConvSpec:
@@ -106,16 +133,15 @@ class Plan:
     """Architecture + memory layout (device independent)."""
 
     def __init__(self, encoder_name, in_ch=3, img=32, ldc=128, K=10, drop_rate=0.0):
-        if "wideresnet" not in encoder_name:
-            raise NotImplementedError("{} not implemented".format(encoder_name))
+        fam = encoder_family(encoder_name)
         if img != 32 or in_ch > CPAD:
             raise NotImplementedError("the MI355X path covers 32x32 inputs with <= 16 channels "
                                       "(BASELINE.json configs); got img=%s ch=%s" % (img, in_ch))
         self.name, self.in_ch, self.img, self.ldc, self.K = encoder_name, in_ch, img, ldc, K
         # nn.Dropout(drop_rate) between conv1 and norm2 of every wide unit (wideresnet.py:23-36); 0 = none (no launch, no key)
         self.drop_rate = float(drop_rate)
-        _, width, n_units = parse_wideresnet(encoder_name)
-        self.widths = [int(16 * width), int(32 * width), int(64 * width)]
+        self.widths = fam["widths"]
+        self.stem_n = fam["stem"]
         self.cfeat = self.widths[-1]
         self.Lpad = _pad16(ldc + K)
         self.NH = 2 * ldc + K
@@ -148,28 +174,32 @@ class Plan:
             return b
 
         enc = "feature_extractor.encoder."
-        self.stem = add_conv(ConvSpec(enc + "pre_process.conv0", "conv", 3, 1, 1, CPAD, 16, img,
+        self.stem = add_conv(ConvSpec(enc + "pre_process.conv0", "conv", 3, 1, 1, CPAD, self.stem_n, img,
                                       cin_real=in_ch))
-        self.stem_bias_off = add_vec(enc + "pre_process.conv0.bias", 16)
-        cin, h = 16, img
+        self.stem_bias_off = add_vec(enc + "pre_process.conv0.bias", self.stem_n)
+        cin, h = self.stem_n, img
         for s, w in enumerate(self.widths):
-            for u in range(n_units):
+            for u in range(fam["units"][s]):
                 stride = 2 if (s > 0 and u == 0) else 1
                 ci = cin if u == 0 else w
-                p = enc + "wideblock%d.wide_block.wideunit%d." % (s + 1, u + 1)
+                p = enc + fam["block"] % (s + 1) + fam["unit"] % (u + 1)
                 unit = dict(cin=ci, cout=w, stride=stride, hin=h)
-                unit["bn1"] = add_bn(p + "f_block.norm1", ci, LEAKY_SLOPE)
+                unit["bn1"] = add_bn(p + "f_block.norm1", ci, fam["slope"])
                 unit["conv1"] = add_conv(ConvSpec(p + "f_block.conv1", "conv", 3, stride, 1, ci, w, h))
-                unit["bn2"] = add_bn(p + "f_block.norm2", w, LEAKY_SLOPE)
+                unit["bn2"] = add_bn(p + "f_block.norm2", w, fam["slope"])
                 unit["conv2"] = add_conv(ConvSpec(p + "f_block.conv2", "conv", 3, 1, 1, w, w, h // stride))
                 if ci != w or stride != 1:
-                    unit["bni"] = add_bn(p + "i_block.norm", ci, LEAKY_SLOPE)
+                    unit["bni"] = add_bn(p + "i_block.norm", ci, fam["slope_i"])
                     unit["convi"] = add_conv(ConvSpec(p + "i_block.conv", "conv", 1, stride, 0, ci, w, h))
                 h //= stride
                 self.units.append(unit)
             cin = w
         self.hfeat = h
-        self.bn_t = add_bn(enc + "transition.norm", self.cfeat, LEAKY_SLOPE)
+        self.bn_t = add_bn(enc + "transition.norm", self.cfeat, fam["slope"])
+        # state_dict prefixes of the sub-modules the reference wraps in nn.DataParallel (data_parallel=True key layout)
+        self.dp_wrapped = tuple([enc + "pre_process"] + [enc + (fam["block"] % (s + 1)).split(".")[0] for s in range(len(self.widths))] +
+                                [enc + "transition", "continuous_inference.mean", "continuous_inference.log_sigma",
+                                 "disc_latent_inference", "feature_reconstructor.decoder"])
         # the three heads share one [2*ldc+K][C] matrix (vae.py:113-129)
         self.head_w_off = alloc(self.NH * self.cfeat)
         self.head_b_off = alloc(self.NH)
@@ -757,7 +787,7 @@ class Engine:
             stat_rep[name] = _replicas(rows)
             n_stat += _align(G * stat_rep[name] * 2 * c)
 
-        stat_slot("t0", 16, B * p.img * p.img)
+        stat_slot("t0", p.stem_n, B * p.img * p.img)
         hs = p.img
         for i, un in enumerate(p.units):
             hs //= un["stride"]
@@ -820,10 +850,10 @@ class Engine:
         f.B, f.G, f.groups, f.temperature, f.training = B, G, groups, temperature, training
         f.Gd = Gd
         f.bnbuf, f.bn_off = bnbuf, bn_off
-        # stem (wideresnet.py:13-14): NCHW fp32 -> NHWC16, conv3x3 + bias, stats of t0
+        # stem (wideresnet.py:13-14, preactresnet.py:8-10): NCHW fp32 -> NHWC16, conv3x3 + bias, stats of t0
         if x16 is None:
             x16 = self.to_nhwc16(image)
-        t = torch.empty(Bt, p.img, p.img, 16, dtype=T, device=dev)
+        t = torch.empty(Bt, p.img, p.img, p.stem_n, dtype=T, device=dev)
         self._igemm(p.stem.geom_fwd(B), x16, pk + es * p.stem.fwd_off, t, bias=pbase + 4 * p.stem_bias_off,
                     stats=sptr("t0"), tag="fwd:stem", groups=G)
         f.x16, f.t, f.c1, f.pro = x16, [t], [], []
@@ -864,7 +894,7 @@ class Engine:
             f.t.append(tout)
             f.pro.append((pro1[:3], pro2[:3], proi[:3] if proi is not None else None))
             h = ho
-        # transition BN + LeakyReLU + global average pool (wideresnet.py:90-91, vae.py:143)
+        # transition BN + LeakyReLU / ReLU + global average pool (wideresnet.py:90-91, preactresnet.py:107-109, vae.py:143)
         prot = finalize(p.bn_t, "t%d" % len(p.units), B * h * h)
         feat = torch.empty(Bt, p.cfeat, dtype=torch.float32, device=dev)
         L.call("sv_pool_fwd", self.code, _vp(f.t[-1].data_ptr()), _vp(prot[0]), _vp(prot[1]), prot[2], Bt, h * h,
@@ -1276,5 +1306,5 @@ class Engine:
         assert deferred is None
         # ---- stem: weight + bias gradients (the image needs none) ---------------------------------
         self._wgrad_async(p.stem.geom_fwd(B), f.x16, None, D, gbase + 4 * p.stem.master_off, tag="wgrad:stem", groups=G)
-        L.call("sv_colsum", self.code, _vp(D.data_ptr()), D.numel() // 16, 16, 16, _vp(gbase + 4 * p.stem_bias_off), st)
+        L.call("sv_colsum", self.code, _vp(D.data_ptr()), D.numel() // p.stem_n, p.stem_n, p.stem_n, _vp(gbase + 4 * p.stem_bias_off), st)
         self._join_side()

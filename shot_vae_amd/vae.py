@@ -8,7 +8,7 @@ the loop of main_shot_vae.py:261-383 runs unchanged.  Differences (all documente
     all-reduce of the flat gradient buffer (see dp.py), not nn.DataParallel;
   * gradients of the parameters are accumulated by the kernels straight into one flat fp32 buffer
     (``p.grad`` are views of it);
-  * only the wideresnet encoders on 32x32 inputs are implemented (the BASELINE.json configs);
+  * the wideresnet-D-W and preactresnet18 / preactresnet34 encoders on 32x32 inputs are implemented;
   * dropout (``drop_rate``) draws one int64 key per training forward (torch.randint, in front of that forward's
     noise) and regenerates its masks from it in the kernels (shotvae_hip.h, sv_dropout_args): the masks differ from
     torch's nn.Dropout draws, their distribution does not.
@@ -19,13 +19,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .engine import Engine, Plan
-
-# modules that the reference wraps in nn.DataParallel (wideresnet.py:78-93, vae.py:108-132, decoder.py:63-64)
-_DP_WRAPPED = ("feature_extractor.encoder.pre_process", "feature_extractor.encoder.wideblock1",
-               "feature_extractor.encoder.wideblock2", "feature_extractor.encoder.wideblock3",
-               "feature_extractor.encoder.transition", "continuous_inference.mean",
-               "continuous_inference.log_sigma", "disc_latent_inference", "feature_reconstructor.decoder")
+from .engine import Engine, Plan, encoder_family
 
 
 class _Node(nn.Module):
@@ -35,8 +29,10 @@ class _Node(nn.Module):
         raise RuntimeError("this sub-module is a parameter container; call the VariationalAutoEncoder")
 
 
-def _dp_key(key):
-    for w in _DP_WRAPPED:
+def _dp_key(key, wrapped):
+    """the data_parallel=True spelling of `key`; wrapped = Plan.dp_wrapped, the modules the reference wraps in nn.DataParallel
+    (wideresnet.py:78-93, preactresnet.py:94-112, vae.py:108-132, decoder.py:63-64)"""
+    for w in wrapped:
         if key.startswith(w + "."):
             return w + ".module." + key[len(w) + 1:]
     return key
@@ -80,10 +76,10 @@ class VariationalAutoEncoder(nn.Module):
                  continuous_latent_dim=100, disc_latent_dim=10, sample_temperature=0.67, small_input=False,
                  compute_dtype="bf16", rng="host"):
         super(VariationalAutoEncoder, self).__init__()
-        if "wideresnet" not in encoder_name:
-            # densenet / preactresnet encoders exist in the reference (vae.py:93-104) but are outside
-            # every BASELINE.json config; same error type as the reference's fall-through (vae.py:106)
-            raise NotImplementedError("{} not implemented".format(encoder_name))
+        # wideresnet-D-W, preactresnet18 / 34; densenet and the bottleneck PreActResNets exist in the reference (vae.py:93-104) but
+        # are not built: NotImplementedError, the reference's fall-through error type (vae.py:106); an unknown preactresnet* name
+        # is the reference's KeyError (preactresnet.py:131)
+        encoder_family(encoder_name)
         drop_rate = float(drop_rate)
         if math.isnan(drop_rate) or drop_rate < 0 or drop_rate > 1:
             raise ValueError("dropout probability has to be between 0 and 1, but got {}".format(drop_rate))
@@ -141,7 +137,7 @@ class VariationalAutoEncoder(nn.Module):
                      "feature_reconstructor"):
             self.add_module(name, _Node())
         for key, kind, payload in plan.state_items():
-            k = _dp_key(key) if self._data_parallel else key
+            k = _dp_key(key, plan.dp_wrapped) if self._data_parallel else key
             parts = k.split(".")
             node = self._node(parts[:-1])
             if kind in ("conv", "mat", "vec"):
@@ -163,7 +159,7 @@ class VariationalAutoEncoder(nn.Module):
             prm.grad = None
         for key, kind, payload in plan.state_items():
             if kind in ("rm", "rv", "nbt"):
-                k = _dp_key(key) if self._data_parallel else key
+                k = _dp_key(key, plan.dp_wrapped) if self._data_parallel else key
                 parts = k.split(".")
                 node = self._node(parts[:-1])
                 if kind == "rm":
@@ -202,7 +198,7 @@ class VariationalAutoEncoder(nn.Module):
                 fixed[k] = v
                 continue
             plain = k.replace(".module.", ".")
-            alt = _dp_key(plain) if self._data_parallel else plain
+            alt = _dp_key(plain, self._plan.dp_wrapped) if self._data_parallel else plain
             fixed[alt if alt in own else k] = v
         out = super(VariationalAutoEncoder, self).load_state_dict(fixed, strict)
         self._engine.mark_dirty()
