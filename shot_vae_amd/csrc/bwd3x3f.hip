@@ -38,7 +38,6 @@
 #include "common.h"
 #include "epilogue.h"
 
-void sv_slab_reduce(const float* ws, int nslabs, int64_t n, float* dw, hipStream_t s);      // wgrad3x3.hip
 int sv_bwd3x3_64(const sv_geom* g, const sv_bwd3x3_args* a, hipStream_t s);                 // bwd3x3g.hip: 64 channels on 16 x 16 maps
 
 namespace {
@@ -505,12 +504,7 @@ int launch(const sv_geom* g, const bwdf_g& PG, int grid, int groups, hipStream_t
     constexpr int WREGS = WLOG == 5 ? SV_BWDF_WREGS : (MODE == 0 ? 1 : 0);      // (as in the kernel)
     constexpr size_t lds = (size_t)2 * (HP * LDF + 128 * LDF + 128 * LDR) * 2 + 2 * CH * 8 + 8 * CH * 4 + (size_t)(2 - WREGS) * 16 * 9 * LDF * 2;
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd3x3f_kernel<WLOG, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(bwd3x3f)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, (int)lds, "bwd3x3f", &bwd3x3f_kernel<WLOG, MODE>)) return rc;
     sv_prof_begin(s);
     hipLaunchKernelGGL((bwd3x3f_kernel<WLOG, MODE>), dim3(grid, groups), dim3(512), lds, s, *g, PG);
     sv_prof_end(s);               // (the event bracket times the main kernel only, like the weight-gradient launchers)

@@ -15,8 +15,6 @@
 #include "common.h"
 #include "epilogue.h"
 
-void sv_slab_reduce(const float* ws, int nslabs, int64_t n, float* dw, hipStream_t s);      // wgrad3x3.hip
-
 namespace {
 
 constexpr int CH = 64, WLOG = 4, W = 16, TR = 4, TP = 64, WP = W + 2;
@@ -484,12 +482,7 @@ __global__ __launch_bounds__(512) void bwd3x3g_kernel(const sv_geom g, const bwd
 template <int MODE>
 int launch_g(const sv_geom* g, const bwdg_g& PG, int grid, int groups, hipStream_t s) {
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&bwd3x3g_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)LDS_BYTES) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(bwd3x3g)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, (int)LDS_BYTES, "bwd3x3g", &bwd3x3g_kernel<MODE>)) return rc;
     sv_prof_begin(s);
     hipLaunchKernelGGL((bwd3x3g_kernel<MODE>), dim3(grid, groups), dim3(512), LDS_BYTES, s, *g, PG);
     sv_prof_end(s);

@@ -306,27 +306,55 @@ struct SvProfScope {
     explicit SvProfScope(void* st) : s((hipStream_t)st) { sv_prof_begin(s); }
     ~SvProfScope() { sv_prof_end(s); }
 };
+// Raises the dynamic-LDS limit of `kernels` (more than 64 KiB per block needs the opt-in; gfx950 has 160 KiB per CU) to `bytes`,
+// once per call site: `done` is the site's own `static bool`, one per kernel instantiation; after the first call this is that
+// flag's test and nothing else.  A failure is reported through sv_check_launch as "hipFuncSetAttribute(<name>)".
+// Like the dispatcher options the flag assumes one device and no concurrent first calls.
+int sv_lds_optin_set(const void* kernel, int bytes, const char* name);      // runtime.hip
+template <typename... K>
+inline int sv_lds_optin(bool& done, int bytes, const char* name, K*... kernels) {
+    if (done) return SV_OK;
+    int rc = SV_OK;
+    ((rc = rc != SV_OK ? rc : sv_lds_optin_set(reinterpret_cast<const void*>(kernels), bytes, name)), ...);
+    done = rc == SV_OK;
+    return rc;
+}
+// exact log2 of a power of two, -1 for anything else (v <= 0 included)
+inline int sv_ilog2_exact(int v) {
+    if (v <= 0 || (v & (v - 1))) return -1;
+    int l = 0;
+    while ((1 << l) < v) ++l;
+    return l;
+}
+// One-block-per-CU launchers: `n` work items (bands, images) dealt to at most `per` blocks in rounds; the smallest grid that
+// needs no more rounds than `per` blocks would.
+inline int sv_block_slots(int n, int per) {
+    if (per < 1) per = 1;
+    if (per > n) per = n;
+    const int rounds = (n + per - 1) / per;
+    return (n + rounds - 1) / rounds;
+}
+// adds `nslabs` partial slabs of n floats (plain stores of a weight-gradient kernel, in ws) to dw in a fixed order (wgrad3x3.hip)
+void sv_slab_reduce(const float* ws, int nslabs, int64_t n, float* dw, hipStream_t s);
 int sv_conv3x3_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
-int sv_hwgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_scale, const float* pro_shift, float pro_slope,
-                  const void* dy, float* dw, float* ws, int64_t ws_elems, int groups, hipStream_t s, int* rc);
 int sv_halo_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
 int sv_tconvr_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
 int sv_sconv_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
 int sv_pconv_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
 int sv_dconv_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
 int sv_thconv_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
-int sv_thwgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_scale, const float* pro_shift, float pro_slope,
-                   const void* dy, float* dw, int groups, hipStream_t s, int* rc);
-// k4wgrad.hip: the thin 4x4 stride-2 layers of svhn_VAE (16 channels at 32x32 <-> 32 channels at 16x16)
-int sv_k4wgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_scale, const float* pro_shift, float pro_slope,
-                   const void* dy, float* dw, float* ws, int64_t ws_elems, int groups, hipStream_t s, int* rc);
-int sv_s2wgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_scale, const float* pro_shift, float pro_slope,
-                   const void* dy, float* dw, int groups, hipStream_t s, int* rc);
 int sv_conv3x3w_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
 int sv_conv3x3x_try(const sv_geom* g, const sv_igemm_args* a, bool fwd, hipStream_t s, int* rc);
-int sv_wgrad3x3_try(const sv_geom* g, int dtype, const void* x, const float* pro_scale, const float* pro_shift,
-                    float pro_slope, const void* dy, float* dw, float* ws, int64_t ws_elems, int groups, hipStream_t s,
-                    int* rc);
+// The specialised candidates of the weight-gradient dispatch (wgrad.hip, whose generic kernels are its tail with the same
+// signature), in its order: each returns 1 and sets *rc when it takes the launch.  `a` is the checked operand block with
+// a.groups normalised (sv_ngroups).
+typedef int sv_wgrad_try_fn(const sv_geom* g, int dtype, const sv_wgrad_args& a, hipStream_t s, int* rc);
+sv_wgrad_try_fn sv_wgrad3x3_try, sv_thwgrad_try, sv_k4wgrad_try, sv_s2wgrad_try, sv_hwgrad_try;
+// the operands every weight-gradient parameter block carries (the structs order them differently)
+template <typename P>
+inline void sv_wg_operands(P& p, const sv_wgrad_args& a) {
+    p.x = a.x; p.pro_scale = a.pro_scale; p.pro_shift = a.pro_shift; p.pro_slope = a.pro_slope; p.dy = a.dy;
+}
 
 #define SV_REQUIRE(cond, code, ...)                \
     do {                                           \

@@ -743,12 +743,8 @@ int launch_m(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const int grid = (nG >= 64 ? ((nG + 7) / 8) * 8 : nG) * nNt;
     const size_t lds = (size_t)(2 * HPIX + WROWS) * LDW * sizeof(T) + 2 * BN * sizeof(double);
     static bool optin = false;
-    if (lds > 64 * 1024 && !optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3m_kernel<T, NT, WLOG, PT>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(conv3x3m)");
-        optin = true;
-    }
+    if (lds > 64 * 1024)
+        if (const int rc = sv_lds_optin(optin, (int)lds, "conv3x3m", &conv3x3m_kernel<T, NT, WLOG, PT>)) return rc;
     SV_LAUNCH_GATE(grid, a);
     sv_prof_begin(s);
     hipLaunchKernelGGL((conv3x3m_kernel<T, NT, WLOG, PT>), dim3(grid, sv_ngroups(a->groups)), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, (int)sizeof(T)));
@@ -781,12 +777,8 @@ int launch_pm(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     chunks = (nT + tiles_per - 1) / tiles_per;
     const size_t lds = (size_t)(HPIX + 32 * 9) * LDW * sizeof(T) + 2 * 32 * sizeof(double);
     static bool optin = false;
-    if (lds > 64 * 1024 && !optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3p_kernel<T, WLOG, CCH, MODE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(conv3x3p)");
-        optin = true;
-    }
+    if (lds > 64 * 1024)
+        if (const int rc = sv_lds_optin(optin, (int)lds, "conv3x3p", &conv3x3p_kernel<T, WLOG, CCH, MODE>)) return rc;
     sv_igemm_args b = *a;          // this kernel folds the BatchNorm finalisation of its prologue (<= 64 channels, <= 64 replicas)
     if (!sv_fold_claim(b.fold_stats && b.fold_replicas <= 64 && (size_t)HPIX * LDW * sizeof(T) >= (size_t)(1024 + 2 * CIN) * 4)) b.fold_stats = nullptr;
     a = &b;
@@ -826,12 +818,8 @@ int launch(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const int grid = (nT >= 64 ? ((nT + 7) / 8) * 8 : nT) * nNt;
     const size_t lds = (size_t)((TR + 2) * (W + 2) + BN * 9) * LDC * sizeof(T) + 2 * BN * sizeof(double);
     static bool optin = false;          // > 64 KiB of dynamic LDS needs an opt-in (gfx950 has 160 KiB per CU)
-    if (lds > 64 * 1024 && !optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<T, NT, WLOG>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(conv3x3)");
-        optin = true;
-    }
+    if (lds > 64 * 1024)
+        if (const int rc = sv_lds_optin(optin, (int)lds, "conv3x3", &conv3x3_kernel<T, NT, WLOG>)) return rc;
     SV_LAUNCH_GATE(grid, a);
     sv_prof_begin(s);
     hipLaunchKernelGGL((conv3x3_kernel<T, NT, WLOG>), dim3(grid, sv_ngroups(a->groups)), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, (int)sizeof(T)));

@@ -380,12 +380,7 @@ int launch_w4(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const int grid = 8 * ((nT + 7) / 8) * nNt;
     const size_t lds = (size_t)C::LDS;
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3w_kernel<NF, WLOG, REV, MODE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(conv3x3w)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, (int)lds, "conv3x3w", &conv3x3w_kernel<NF, WLOG, REV, MODE>)) return rc;
     // BatchNorm finalisation folded into this launch: the blocks sum the replicas themselves (256 threads = 256 / Cin parts)
     sv_igemm_args b = *a;
     if (!sv_fold_claim(b.fold_stats && 256 % g->Cin == 0 && b.fold_replicas <= 64 && (size_t)(1024 + 2 * g->Cin) * 4 <= (size_t)C::HB))

@@ -653,12 +653,7 @@ int launch_x4(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const int grid = 8 * (items_xcd < cap ? items_xcd : cap);
     const size_t lds = (size_t)C::LDS;
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3x_kernel<WLOG, REV, MODE, DMAH>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(conv3x3x)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, (int)lds, "conv3x3x", &conv3x3x_kernel<WLOG, REV, MODE, DMAH>)) return rc;
     SV_LAUNCH_GATE(grid, a);          // (deterministic mode: a replica per block -- the gate checks replicas >= 4 * grid)
     sv_prof_begin(s);
     hipLaunchKernelGGL((conv3x3x_kernel<WLOG, REV, MODE, DMAH>), dim3(grid, G), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, 2));

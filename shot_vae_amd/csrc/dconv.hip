@@ -232,17 +232,9 @@ int launch_dconv(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     typedef dconv_cfg<NOUT_> C;
     const int G = sv_ngroups(a->groups);
     const int nband = g->B * (g->Hout / C::BR);
-    int per = sv_persistent_blocks() / 2 / G;          // (the budget counts two blocks per CU; this kernel is one)
-    if (per < 1) per = 1;
-    if (per > nband) per = nband;
-    const int rounds = (nband + per - 1) / per;
-    const int grid = (nband + rounds - 1) / rounds;
+    const int grid = sv_block_slots(nband, sv_persistent_blocks() / 2 / G);      // (the budget counts two blocks per CU; this kernel is one)
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&dconv_kernel<NOUT_, EX_>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(dconv)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, C::LDS, "dconv", &dconv_kernel<NOUT_, EX_>)) return rc;
     int gate_rc = SV_OK;
     if (sv_dry_run(grid, a, &gate_rc)) return gate_rc;
     sv_prof_begin(s);

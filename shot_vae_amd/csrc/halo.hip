@@ -720,12 +720,8 @@ int launch_halop_pv(const sv_geom* g, const sv_igemm_args* a, const halo_cfg& c,
     const int tiles_per = (nT + chunks - 1) / chunks;
     chunks = (nT + tiles_per - 1) / tiles_per;
     static bool optin = false;
-    if (lds > 64 * 1024 && !optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&halop_kernel<T, NT, CC, NPH, PV, OCC, MODE>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(halop)");
-        optin = true;
-    }
+    if (lds > 64 * 1024)
+        if (const int rc = sv_lds_optin(optin, 160 * 1024, "halop", &halop_kernel<T, NT, CC, NPH, PV, OCC, MODE>)) return rc;
     sv_igemm_args b = *a;          // the persistent kernel folds the BatchNorm finalisation of its prologue (fold_*)
     if (!sv_fold_claim(b.fold_stats && b.fold_replicas <= 64 && 256 % g->Cin == 0 && (size_t)c.HP * (g->Cin + 16) * sizeof(T) >= (1024 + 2 * 64) * 4))
         b.fold_stats = nullptr;
@@ -779,12 +775,6 @@ int launch_halop_nt(const sv_geom* g, const sv_igemm_args* a, const halo_cfg& c,
     return nt == 2 ? launch_halop<T, 2, CC, NPH>(g, a, c, lds, s) : launch_halop<T, 1, CC, NPH>(g, a, c, lds, s);
 }
 
-int ilog2x(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return (1 << l) == v ? l : -1;
-}
-
 template <typename T, int NT, int CC, int NPH>
 int launch_halo(const sv_geom* g, const sv_igemm_args* a, const halo_cfg& c, hipStream_t s) {
     constexpr int BN = 16 * NT;
@@ -794,12 +784,8 @@ int launch_halo(const sv_geom* g, const sv_igemm_args* a, const halo_cfg& c, hip
     const size_t lds = ((size_t)c.HP * (CC + 16) + (size_t)BN * (c.tslots * CC + 16)) * sizeof(T) + 2 * BN * sizeof(double) +
                        256 * 8 * sizeof(T);       // + the per-thread dummy vectors of the branch-free staging
     static bool optin = false;
-    if (lds > 64 * 1024 && !optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&halo_kernel<T, NT, CC, NPH>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(halo)");
-        optin = true;
-    }
+    if (lds > 64 * 1024)
+        if (const int rc = sv_lds_optin(optin, 160 * 1024, "halo", &halo_kernel<T, NT, CC, NPH>)) return rc;
     SV_LAUNCH_GATE(grid, a);
     sv_prof_begin(s);
     hipLaunchKernelGGL((halo_kernel<T, NT, CC, NPH>), dim3(grid, sv_ngroups(a->groups)), dim3(256), lds, s, *g,
@@ -828,8 +814,8 @@ int sv_halo_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t
     if (g->Hq != g->Wq || g->Hin != g->Win || g->sy != g->sx || g->osy != g->osx) return 0;
     if (g->sy < 1 || g->sy > 2) return 0;
     halo_cfg c;
-    c.wlog = ilog2x(g->Wq);
-    c.hlog = ilog2x(g->Hq);
+    c.wlog = sv_ilog2_exact(g->Wq);
+    c.hlog = sv_ilog2_exact(g->Hq);
     if (c.wlog < 1 || c.wlog > 5) return 0;              // 2 .. 32 columns (1 x 1 maps are plain GEMMs: igemm.hip)
     if (g->Cin % 16 != 0 || g->N % 16 != 0 || g->ldx != g->Cin) return 0;
     if (g->Cin % 32 != 0 && g->Cin != 16) return 0;
@@ -848,7 +834,7 @@ int sv_halo_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t
     const int Wq = g->Wq, Hq = g->Hq;
     c.TR = 128 / Wq;
     const int HH = c.TR < Hq ? c.TR : Hq;
-    c.hhlog = ilog2x(HH);
+    c.hhlog = sv_ilog2_exact(HH);
     c.SEG = c.TR / HH;
     c.SR = g->sy * (HH - 1) + (dymax - dymin) + 1;
     c.LW = g->sx * (Wq - 1) + (dxmax - dxmin) + 1;

@@ -20,8 +20,6 @@
 
 #include "common.h"
 
-void sv_slab_reduce(const float* ws, int nslabs, int64_t n, float* dw, hipStream_t s);      // wgrad3x3.hip
-
 namespace {
 
 
@@ -229,23 +227,13 @@ __global__ __launch_bounds__(256, 2) void hwgrad_kernel(const sv_geom g, const s
     }
 }
 
-int ilog2h(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return (1 << l) == v ? l : -1;
-}
-
 template <int NS, int CS, int NPH>
 int launch_hw(const sv_geom* g, const hw_params& p, float* dw, size_t lds, hipStream_t s) {
     constexpr int KPARTS = 4 / ((NS / 16) * (CS / 16));
     const int nNC = (g->N / NS) * (g->Cin / CS);
     static bool optin = false;
-    if (lds > 64 * 1024 && !optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&hwgrad_kernel<NS, CS, NPH>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(hwgrad)");
-        optin = true;
-    }
+    if (lds > 64 * 1024)
+        if (const int rc = sv_lds_optin(optin, 160 * 1024, "hwgrad", &hwgrad_kernel<NS, CS, NPH>)) return rc;
     sv_prof_begin(s);
     hipLaunchKernelGGL((hwgrad_kernel<NS, CS, NPH>), dim3(p.splits * nNC, p.groups), dim3(256), lds, s, *g,
                        sv_expand_wg(*g, p, p.groups, 2));
@@ -258,16 +246,16 @@ int launch_hw(const sv_geom* g, const hw_params& p, float* dw, size_t lds, hipSt
 
 // Returns 1 and sets *rc when the geometry is covered (bf16, square power-of-two grids, <= 4 taps per phase with four phases
 // or <= 16 taps with one, the tile's LDS image within budget) and the caller's workspace holds the partial slabs.
-int sv_hwgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_scale, const float* pro_shift, float pro_slope,
-                  const void* dy, float* dw, float* ws, int64_t ws_elems, int groups, hipStream_t s, int* rc) {
-    if (sv_disabled(SV_K_HWGRAD) || dtype != SV_BF16 || !ws) return 0;
+int sv_hwgrad_try(const sv_geom* g, int dtype, const sv_wgrad_args& a, hipStream_t s, int* rc) {
+    if (sv_disabled(SV_K_HWGRAD) || dtype != SV_BF16 || !a.ws) return 0;
+    const int groups = a.groups;
     if (g->Hq != g->Wq || g->Hin != g->Win || g->sy != g->sx || g->osy != g->osx) return 0;
     if (g->sy < 1 || g->sy > 2 || g->osy < 1 || g->osy > 2) return 0;
     if (g->nphase != 1 && g->nphase != 4) return 0;
     if (g->ldx != g->Cin || g->ldo != g->N || g->Cin % 16 != 0 || g->N % 16 != 0) return 0;
     hw_params p;
-    p.wlog = ilog2h(g->Wq);
-    p.hlog = ilog2h(g->Hq);
+    p.wlog = sv_ilog2_exact(g->Wq);
+    p.hlog = sv_ilog2_exact(g->Hq);
     if (p.wlog < 2 || p.wlog > 5) return 0;                  // 4 .. 32 columns
     int dymin = 127, dymax = -127, dxmin = 127, dxmax = -127, ttot = 0;
     for (int ph = 0; ph < g->nphase; ++ph) {
@@ -285,7 +273,7 @@ int sv_hwgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_s
     const int Wq = g->Wq, Hq = g->Hq, os = g->osy;
     p.TR = 128 / Wq;
     const int HH = p.TR < Hq ? p.TR : Hq;
-    p.hhlog = ilog2h(HH);
+    p.hhlog = sv_ilog2_exact(HH);
     p.SEG = p.TR / HH;
     p.SR = g->sy * (HH - 1) + (dymax - dymin) + 1;
     p.LW = g->sx * (Wq - 1) + (dxmax - dxmin) + 1;
@@ -320,13 +308,14 @@ int sv_hwgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_s
     // 97 -> 106 us): those stay on the generic kernel (SV_OPT_HALO_ALL = 1 takes the whole range: tests)
     if (!sv_halo_all() && !(nNC <= 2 && g->sy == 1)) return 0;
     const int64_t need = (int64_t)splits * groups * kparts * g->N * g->T_orig * g->Cin;
-    if (ws_elems < need) return 0;
-    p.x = x; p.pro_scale = pro_scale; p.pro_shift = pro_shift; p.pro_slope = pro_slope; p.dy = dy; p.ws = ws;
+    if (a.ws_elems < need) return 0;
+    sv_wg_operands(p, a);
+    p.ws = a.ws;
     p.splits = splits; p.groups = groups;
     const bool multi = g->nphase == 4;
-    if (NS == 32 && CS == 32) *rc = multi ? launch_hw<32, 32, 4>(g, p, dw, lds, s) : launch_hw<32, 32, 1>(g, p, dw, lds, s);
-    else if (NS == 32 && CS == 16) *rc = multi ? launch_hw<32, 16, 4>(g, p, dw, lds, s) : launch_hw<32, 16, 1>(g, p, dw, lds, s);
-    else if (NS == 16 && CS == 32) *rc = multi ? launch_hw<16, 32, 4>(g, p, dw, lds, s) : launch_hw<16, 32, 1>(g, p, dw, lds, s);
-    else *rc = multi ? launch_hw<16, 16, 4>(g, p, dw, lds, s) : launch_hw<16, 16, 1>(g, p, dw, lds, s);
+    if (NS == 32 && CS == 32) *rc = multi ? launch_hw<32, 32, 4>(g, p, a.dw, lds, s) : launch_hw<32, 32, 1>(g, p, a.dw, lds, s);
+    else if (NS == 32 && CS == 16) *rc = multi ? launch_hw<32, 16, 4>(g, p, a.dw, lds, s) : launch_hw<32, 16, 1>(g, p, a.dw, lds, s);
+    else if (NS == 16 && CS == 32) *rc = multi ? launch_hw<16, 32, 4>(g, p, a.dw, lds, s) : launch_hw<16, 32, 1>(g, p, a.dw, lds, s);
+    else *rc = multi ? launch_hw<16, 16, 4>(g, p, a.dw, lds, s) : launch_hw<16, 16, 1>(g, p, a.dw, lds, s);
     return 1;
 }

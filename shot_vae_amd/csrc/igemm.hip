@@ -525,12 +525,8 @@ int launch_dma(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const int grid = (nMt >= 64 ? ((nMt + 7) / 8) * 8 : nMt) * nNt * g->nphase;
     const size_t lds = (size_t)3 * (BM + BN) * 64;
     static bool optin = false;
-    if (lds > 64 * 1024 && !optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_dma_kernel<NT, MS>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(igemm_dma)");
-        optin = true;
-    }
+    if (lds > 64 * 1024)
+        if (const int rc = sv_lds_optin(optin, (int)lds, "igemm_dma", &igemm_dma_kernel<NT, MS>)) return rc;
     SV_LAUNCH_GATE(grid, a);
     sv_prof_begin(s);
     hipLaunchKernelGGL((igemm_dma_kernel<NT, MS>), dim3(grid, sv_ngroups(a->groups)), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, 2));
@@ -547,12 +543,8 @@ int launch_al(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const int grid = (nMt >= 64 ? ((nMt + 7) / 8) * 8 : nMt) * nNt * g->nphase;
     const size_t lds = (size_t)2 * (BM + BN) * LDK * sizeof(T) + (MS == 4 ? 0 : 2 * BN * sizeof(double));
     static bool optin = false;
-    if (lds > 64 * 1024 && !optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<T, NT, KV, MS, AL>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(igemm)");
-        optin = true;
-    }
+    if (lds > 64 * 1024)
+        if (const int rc = sv_lds_optin(optin, (int)lds, "igemm", &igemm_kernel<T, NT, KV, MS, AL>)) return rc;
     SV_LAUNCH_GATE(grid, a);
     sv_prof_begin(s);
     hipLaunchKernelGGL((igemm_kernel<T, NT, KV, MS, AL>), dim3(grid, sv_ngroups(a->groups)), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, (int)sizeof(T)));

@@ -15,8 +15,6 @@
 // Same sv_wgrad contract: a fast path inside it (SV_K_THWGRAD disables); declines the deterministic mode.
 #include "common.h"
 
-void sv_slab_reduce(const float* ws, int nslabs, int64_t n, float* dw, hipStream_t s);      // wgrad3x3.hip
-
 namespace {
 
 struct k4wg_params {
@@ -179,12 +177,12 @@ __global__ __launch_bounds__(512, 1) void k4wgrad_kernel(const int B, const sv_w
 
 // Returns 1 and sets *rc when the launch is the weight gradient of Conv2d(16, 32, 4, 2, 1) at 32x32 or of ConvTranspose2d(32, 16, 4, 2, 1)
 // at 16x16.
-int sv_k4wgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_scale, const float* pro_shift, float pro_slope,
-                   const void* dy, float* dw, float* ws, int64_t ws_elems, int groups, hipStream_t s, int* rc) {
+int sv_k4wgrad_try(const sv_geom* g, int dtype, const sv_wgrad_args& a, hipStream_t s, int* rc) {
     typedef k4wg_cfg C;
     if (sv_disabled(SV_K_THWGRAD) || dtype != SV_BF16 || sv_deterministic() || g->T_orig != 16) return 0;
     k4wg_params p;
-    p.pro_scale = pro_scale; p.pro_shift = pro_shift; p.pro_slope = pro_slope; p.dw = dw;
+    p.pro_scale = a.pro_scale; p.pro_shift = a.pro_shift; p.pro_slope = a.pro_slope; p.dw = a.dw;
+    const int groups = a.groups;
     bool seen[16] = {};
     int torig[16];
     if (g->nphase == 1 && g->sy == 2 && g->sx == 2 && g->osy == 1 && g->osx == 1) {
@@ -198,7 +196,7 @@ int sv_k4wgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_
             seen[4 * ky + kx] = true;
             p.ky[t] = (int8_t)ky; p.kx[t] = (int8_t)kx; torig[t] = P.torig[t];
         }
-        p.small = dy; p.big = x; p.pro_on_small = 0; p.transposed = 0;
+        p.small = a.dy; p.big = a.x; p.pro_on_small = 0; p.transposed = 0;
     } else if (g->nphase == 4 && g->sy == 1 && g->sx == 1 && g->osy == 2 && g->osx == 2) {
         // the transposed convolution: small = x, big = dy; phase (py, px), input offset (dy, dx) <-> kernel position (py + 1 - 2 dy, px + 1 - 2 dx)
         if (g->Cin != 32 || g->ldx != 32 || g->N != 16 || g->ldo != 16 || g->Hin != 16 || g->Win != 16 || g->Hout != 32 || g->Wout != 32) return 0;
@@ -213,26 +211,16 @@ int sv_k4wgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_
                 p.ky[n] = (int8_t)ky; p.kx[n] = (int8_t)kx; torig[n] = P.torig[t];
             }
         }
-        p.small = x; p.big = dy; p.pro_on_small = 1; p.transposed = 1;
+        p.small = a.x; p.big = a.dy; p.pro_on_small = 1; p.transposed = 1;
     } else {
         return 0;
     }
     for (int t = 0; t < 16; ++t) p.slot_of[torig[t]] = (int8_t)t;
     if (g->B < 1) return 0;
-    int per = sv_persistent_blocks() / 2 / groups;                 // one block per CU
-    if (per < 1) per = 1;
-    if (per > g->B) per = g->B;
-    const int rounds = (g->B + per - 1) / per;
-    const int grid = (g->B + rounds - 1) / rounds;
+    const int grid = sv_block_slots(g->B, sv_persistent_blocks() / 2 / groups);      // one block per CU
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k4wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess) {
-            *rc = sv_check_launch("hipFuncSetAttribute(k4wgrad)");
-            return 1;
-        }
-        optin = true;
-    }
-    p.slabs = (ws && ws_elems >= (int64_t)grid * groups * 8192) ? ws : nullptr;
+    if ((*rc = sv_lds_optin(optin, C::LDS, "k4wgrad", &k4wgrad_kernel))) return 1;
+    p.slabs = (a.ws && a.ws_elems >= (int64_t)grid * groups * 8192) ? a.ws : nullptr;
     // the groups' operands follow each other (sv_expand_wg works on the fields x / dy of the convolution's view: redo it here)
     sv_wg_g<k4wg_params> PG;
     const int64_t ss = (int64_t)g->B * 256 * 32 * 2, bs = (int64_t)g->B * 1024 * 16 * 2;
@@ -248,7 +236,7 @@ int sv_k4wgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_
     sv_prof_begin(s);
     hipLaunchKernelGGL(k4wgrad_kernel, dim3(grid, groups), dim3(C::NTH), C::LDS, s, g->B, PG);
     sv_prof_end(s);
-    if (p.slabs) sv_slab_reduce(p.slabs, grid * groups, 8192, dw, s);
+    if (p.slabs) sv_slab_reduce(p.slabs, grid * groups, 8192, a.dw, s);
     *rc = sv_check_launch("sv_wgrad(k4wgrad)");
     return 1;
 }

@@ -27,6 +27,13 @@ int sv_check_launch(const char* what) {
     return SV_OK;
 }
 
+int sv_lds_optin_set(const void* kernel, int bytes, const char* name) {
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess) return SV_OK;
+    char what[64];
+    snprintf(what, sizeof(what), "hipFuncSetAttribute(%s)", name);
+    return sv_check_launch(what);
+}
+
 namespace {
 int g_disable_mask = 0;
 int g_wide_min_blocks = 256;

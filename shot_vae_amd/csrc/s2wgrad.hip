@@ -184,17 +184,9 @@ template <typename C>
 int launch_s2wgrad(const sv_geom* g, const s2wg_params& p, int groups, hipStream_t s) {
     constexpr int nparts = C::NTOT / C::NB;
     const int nband = g->B * (C::WO / 8);
-    int per = sv_persistent_blocks() / 2 / groups / nparts;        // band slots: one block per CU, nparts blocks per slot
-    if (per < 1) per = 1;
-    if (per > nband) per = nband;
-    const int rounds = (nband + per - 1) / per;
-    const int slots = (nband + rounds - 1) / rounds;
+    const int slots = sv_block_slots(nband, sv_persistent_blocks() / 2 / groups / nparts);      // band slots: one block per CU, nparts blocks per slot
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&s2wgrad_kernel<C>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(s2wgrad)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, C::LDS, "s2wgrad", &s2wgrad_kernel<C>)) return rc;
     sv_prof_begin(s);
     hipLaunchKernelGGL((s2wgrad_kernel<C>), dim3(slots * nparts, groups), dim3(C::NTH), C::LDS, s, *g, sv_expand_wg(*g, p, groups, 2), nparts);
     sv_prof_end(s);
@@ -205,8 +197,7 @@ int launch_s2wgrad(const sv_geom* g, const s2wg_params& p, int groups, hipStream
 
 // Returns 1 and sets *rc when the launch is the weight gradient of a stride-2 3x3 convolution of the WideResNet: 32 -> 64 at 32x32,
 // 64 -> 128 at 16x16.
-int sv_s2wgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_scale, const float* pro_shift, float pro_slope,
-                   const void* dy, float* dw, int groups, hipStream_t s, int* rc) {
+int sv_s2wgrad_try(const sv_geom* g, int dtype, const sv_wgrad_args& a, hipStream_t s, int* rc) {
     if (sv_disabled(SV_K_S2WGRAD) || dtype != SV_BF16 || sv_deterministic()) return 0;
     if (g->nphase != 1 || g->sy != 2 || g->sx != 2 || g->osy != 1 || g->osx != 1) return 0;
     const sv_phase& P = g->phase[0];
@@ -215,8 +206,9 @@ int sv_s2wgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_
         if (P.dy[t] < -1 || P.dy[t] > 1 || P.dx[t] < -1 || P.dx[t] > 1) return 0;
     if (g->Hin != g->Win || g->Hout != g->Wout || g->Hin != 2 * g->Hout || g->ldx != g->Cin || g->ldo != g->N) return 0;
     s2wg_params p;
-    p.x = x; p.dy = dy; p.pro_scale = pro_scale; p.pro_shift = pro_shift; p.pro_slope = pro_slope; p.dw = dw;
-    if (g->Cin == 32 && g->N == 64 && g->Hout == 16) { *rc = launch_s2wgrad<s2wg_cfg<32, 64, 64, 16>>(g, p, groups, s); return 1; }
-    if (g->Cin == 64 && g->N == 128 && g->Hout == 8) { *rc = launch_s2wgrad<s2wg_cfg<64, 32, 128, 8>>(g, p, groups, s); return 1; }
+    sv_wg_operands(p, a);
+    p.dw = a.dw;
+    if (g->Cin == 32 && g->N == 64 && g->Hout == 16) { *rc = launch_s2wgrad<s2wg_cfg<32, 64, 64, 16>>(g, p, a.groups, s); return 1; }
+    if (g->Cin == 64 && g->N == 128 && g->Hout == 8) { *rc = launch_s2wgrad<s2wg_cfg<64, 32, 128, 8>>(g, p, a.groups, s); return 1; }
     return 0;
 }

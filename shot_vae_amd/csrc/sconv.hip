@@ -295,18 +295,9 @@ int launch_sconv(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     typedef sconv_cfg<CIN, NOUT, W> C;
     const int G = sv_ngroups(a->groups);
     const int nband = g->B * (g->Hout / 8);
-    int per = sv_persistent_blocks() / 2 / G;          // (the budget counts two blocks per CU; this kernel is one)
-    if (per < 1) per = 1;
-    if (per > nband) per = nband;
-    const int rounds = (nband + per - 1) / per;
-    const int grid = (nband + rounds - 1) / rounds;
+    const int grid = sv_block_slots(nband, sv_persistent_blocks() / 2 / G);      // (the budget counts two blocks per CU; this kernel is one)
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&sconv_kernel<CIN, NOUT, W>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                C::LDS) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(sconv)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, C::LDS, "sconv", &sconv_kernel<CIN, NOUT, W>)) return rc;
     sv_igemm_args b = *a;          // this kernel folds the BatchNorm finalisation of its prologue
     if (!sv_fold_claim(b.fold_stats != nullptr)) b.fold_stats = nullptr;
     a = &b;

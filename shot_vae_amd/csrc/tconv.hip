@@ -490,19 +490,10 @@ template <int CIN, int NOUT, int H, bool EX>
 int launch_tconvr(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     typedef tconvr_cfg<CIN, NOUT, H> C;
     const int G = sv_ngroups(a->groups);
-    int per = sv_persistent_blocks() / 2 / G;          // (the budget counts two blocks per CU; this kernel is one: 512 registers)
-    if (per < 1) per = 1;
-    if (per > g->B) per = g->B;
     // equal shares: every block the same number of images where the batch allows it
-    const int rounds = (g->B + per - 1) / per;
-    const int grid = (g->B + rounds - 1) / rounds;
+    const int grid = sv_block_slots(g->B, sv_persistent_blocks() / 2 / G);      // (the budget counts two blocks per CU; this kernel is one: 512 registers)
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&tconvr_kernel<CIN, NOUT, H, EX>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                C::LDS) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(tconvr)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, C::LDS, "tconvr", &tconvr_kernel<CIN, NOUT, H, EX>)) return rc;
     sv_igemm_args b = *a;          // the forward form folds the BatchNorm finalisation of its prologue
     if (!sv_fold_claim(!EX && b.fold_stats != nullptr)) b.fold_stats = nullptr;
     a = &b;
@@ -812,17 +803,9 @@ template <bool FWD>
 int launch_tconvx16(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     typedef tconvx16_cfg C;
     const int G = sv_ngroups(a->groups);
-    int per = sv_persistent_blocks() / 2 / G;
-    if (per < 1) per = 1;
-    if (per > g->B) per = g->B;
-    const int rounds = (g->B + per - 1) / per;
-    const int grid = (g->B + rounds - 1) / rounds;
+    const int grid = sv_block_slots(g->B, sv_persistent_blocks() / 2 / G);
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&tconvx16_kernel<FWD>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(tconvx16)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, C::LDS, "tconvx16", &tconvx16_kernel<FWD>)) return rc;
     sv_igemm_args b = *a;          // the forward form folds the BatchNorm finalisation of its prologue
     if (!sv_fold_claim(FWD && b.fold_stats != nullptr)) b.fold_stats = nullptr;
     a = &b;

@@ -241,11 +241,7 @@ int launch_thconv(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     typedef thconv_cfg<CIN, NOUT> C;
     const int G = sv_ngroups(a->groups);
     const int nband = g->B * (C::W / 8);
-    int per = sv_persistent_blocks() / 2 / G;          // (the budget counts two blocks per CU; this kernel is one)
-    if (per < 1) per = 1;
-    if (per > nband) per = nband;
-    const int rounds = (nband + per - 1) / per;
-    const int grid = (nband + rounds - 1) / rounds;
+    const int grid = sv_block_slots(nband, sv_persistent_blocks() / 2 / G);      // (the budget counts two blocks per CU; this kernel is one)
     SV_LAUNCH_GATE(grid, a);
     sv_prof_begin(s);
     hipLaunchKernelGGL((thconv_kernel<CIN, NOUT>), dim3(grid, G), dim3(C::NTH), C::LDS, s, *g, sv_expand_groups(*g, *a, 2));

@@ -199,17 +199,9 @@ int launch_thwgrad(const sv_geom* g, const thwg_params& p, int groups, hipStream
     typedef thwg_cfg<NOUT, NTOT> C;
     constexpr int nparts = NTOT / NOUT;
     const int nband = g->B * (32 / C::BR);
-    int per = sv_persistent_blocks() / 2 / groups / nparts;        // band slots: one block per CU, nparts blocks per slot
-    if (per < 1) per = 1;
-    if (per > nband) per = nband;
-    const int rounds = (nband + per - 1) / per;
-    const int slots = (nband + rounds - 1) / rounds;
+    const int slots = sv_block_slots(nband, sv_persistent_blocks() / 2 / groups / nparts);      // band slots: one block per CU, nparts blocks per slot
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&thwgrad_kernel<NOUT, NTOT>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(thwgrad)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, C::LDS, "thwgrad", &thwgrad_kernel<NOUT, NTOT>)) return rc;
     sv_prof_begin(s);
     hipLaunchKernelGGL((thwgrad_kernel<NOUT, NTOT>), dim3(slots * nparts, groups), dim3(C::NTH), C::LDS, s, *g, sv_expand_wg(*g, p, groups, 2), nparts);
     sv_prof_end(s);
@@ -219,8 +211,7 @@ int launch_thwgrad(const sv_geom* g, const thwg_params& p, int groups, hipStream
 }  // namespace
 
 // Returns 1 and sets *rc when the launch is the weight gradient of a thin stride-1 3x3 layer at 32x32 (16 input channels).
-int sv_thwgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_scale, const float* pro_shift, float pro_slope,
-                   const void* dy, float* dw, int groups, hipStream_t s, int* rc) {
+int sv_thwgrad_try(const sv_geom* g, int dtype, const sv_wgrad_args& a, hipStream_t s, int* rc) {
     if (sv_disabled(SV_K_THWGRAD) || dtype != SV_BF16 || sv_deterministic()) return 0;
     if (g->nphase != 1 || g->sy != 1 || g->sx != 1 || g->osy != 1 || g->osx != 1) return 0;
     const sv_phase& P = g->phase[0];
@@ -229,9 +220,10 @@ int sv_thwgrad_try(const sv_geom* g, int dtype, const void* x, const float* pro_
         if (P.dy[t] < -1 || P.dy[t] > 1 || P.dx[t] < -1 || P.dx[t] > 1) return 0;
     if (g->Cin != 16 || g->ldx != 16 || g->Hin != 32 || g->Win != 32 || g->Hout != 32 || g->Wout != 32 || g->ldo != g->N) return 0;
     thwg_params p;
-    p.x = x; p.dy = dy; p.pro_scale = pro_scale; p.pro_shift = pro_shift; p.pro_slope = pro_slope; p.dw = dw;
-    if (g->N == 32) { *rc = launch_thwgrad<32>(g, p, groups, s); return 1; }
-    if (g->N == 16) { *rc = launch_thwgrad<16>(g, p, groups, s); return 1; }
-    if (g->N == 160) { *rc = launch_thwgrad<32, 160>(g, p, groups, s); return 1; }
+    sv_wg_operands(p, a);
+    p.dw = a.dw;
+    if (g->N == 32) { *rc = launch_thwgrad<32>(g, p, a.groups, s); return 1; }
+    if (g->N == 16) { *rc = launch_thwgrad<16>(g, p, a.groups, s); return 1; }
+    if (g->N == 160) { *rc = launch_thwgrad<32, 160>(g, p, a.groups, s); return 1; }
     return 0;
 }

@@ -14,8 +14,6 @@
 
 #include "common.h"
 
-void sv_slab_reduce(const float* ws, int nslabs, int64_t n, float* dw, hipStream_t s);      // wgrad3x3.hip
-
 namespace {
 
 constexpr int RW = 32;   // rows (output positions) per wave per iteration = one MFMA k chunk
@@ -531,13 +529,6 @@ int launch_c(const sv_geom* g, wg_params p, int64_t M, hipStream_t s, float* det
     return sv_check_launch("sv_wgrad(wide)");
 }
 
-int ilog2_exact(int v) {
-    if (v <= 0 || (v & (v - 1))) return -1;
-    int s = 0;
-    while ((1 << s) < v) ++s;
-    return s;
-}
-
 template <typename T, int TN, int TC, bool USE_TR, bool FAST, bool INCR>
 int launch2(const sv_geom* g, const wg_params& p, hipStream_t s) {
     constexpr int BNw = 16 * TN, BCw = 16 * TC;
@@ -584,75 +575,30 @@ int dispatch(const sv_geom* g, const wg_params& p, int tn, int tc, hipStream_t s
 
 static_assert(sizeof(sv_wgrad_args) == 80 && sizeof(sv_igemm_args) == 224 && sizeof(sv_param_job) == 112 && sizeof(sv_bwd3x3_args) == 224, "ABI 8 struct layout (tests/test_abi_cpu.py)");
 
-extern "C" int sv_wgrad_ex(const sv_geom* g, int dtype, const sv_wgrad_args* a, void* stream) {
-    SV_REQUIRE(g && a, SV_E_ARG, "sv_wgrad_ex: null argument");
-    SV_REQUIRE(a->block_budget == 0 || a->block_budget >= 8, SV_E_ARG, "sv_wgrad_ex: block_budget=%d", a->block_budget);
-    SvBudgetScope budget_scope(a->block_budget);
-    return sv_wgrad(g, dtype, a->x, a->pro_scale, a->pro_shift, a->pro_slope, a->dy, a->dw, a->splits, a->use_tr, a->ws,
-                    a->ws_elems, a->groups, stream);
-}
-
-extern "C" int sv_wgrad(const sv_geom* g, int dtype, const void* x, const float* pro_scale,
-                        const float* pro_shift, float pro_slope, const void* dy, float* dw, int splits,
-                        int use_tr, float* ws, int64_t ws_elems, int groups, void* stream) {
-    SV_REQUIRE(g && x && dy && dw, SV_E_ARG, "sv_wgrad: null argument");
-    SV_REQUIRE(dtype == SV_F32 || dtype == SV_BF16, SV_E_ARG, "sv_wgrad: bad dtype %d", dtype);
-    SV_REQUIRE(g->Cin % 16 == 0 && g->N % 16 == 0 && g->ldx % 8 == 0 && g->ldo % 8 == 0, SV_E_SHAPE,
-               "sv_wgrad: Cin=%d N=%d must be multiples of 16", g->Cin, g->N);
-    SV_REQUIRE(!pro_scale || pro_shift, SV_E_ARG, "sv_wgrad: prologue shift missing");
-    SV_REQUIRE(groups >= 0 && groups <= SV_MAX_GROUPS, SV_E_ARG, "sv_wgrad: groups=%d (at most %d)", groups, SV_MAX_GROUPS);
-    SV_REQUIRE(!pro_scale || (pro_slope >= 0.f && pro_slope <= 1.f), SV_E_ARG,
-               "sv_wgrad: activation slope %g outside [0, 1]", (double)pro_slope);
-    if (sv_deterministic() && sv_ngroups(groups) > 1) {
-        // fixed summation order: the groups of a batched launch one after the other (stream order), each a launch whose
-        // blocks add ONCE per weight (partial slabs + ordered reduction, or a single M range of the generic kernel)
-        const int es = dtype == SV_BF16 ? 2 : 4;
-        const int64_t xs = (int64_t)g->B * g->Hin * g->Win * g->ldx * es, ys = (int64_t)g->B * g->Hout * g->Wout * g->ldo * es;
-        for (int grp = 0; grp < groups; ++grp) {
-            const int rc = sv_wgrad(g, dtype, reinterpret_cast<const char*>(x) + grp * xs, pro_scale ? pro_scale + grp * g->Cin : nullptr,
-                                    pro_shift ? pro_shift + grp * g->Cin : nullptr, pro_slope,
-                                    reinterpret_cast<const char*>(dy) + grp * ys, dw, splits, use_tr, ws, ws_elems, 1, stream);
-            if (rc != SV_OK) return rc;
-        }
-        return SV_OK;
-    }
-    // deterministic mode, generic kernels: one adder per weight -- the m ranges write slabs of their own in the caller's
-    // workspace and a fixed-order pass adds them to dw (without a workspace: a single m range)
-    const int det_cap = sv_deterministic() ? det_slabs_cap(g, ws, ws_elems) : 0;
-    if (sv_deterministic()) splits = det_cap ? 0 : 1;
-    if (dtype == SV_F32 || use_tr) {   // stride-1 3x3: LDS-halo kernels (wgrad3x3.hip) unless switched off
-        int rc = 0;
-        if (!sv_disabled(SV_K_WGRAD3X3) && sv_wgrad3x3_try(g, dtype, x, pro_scale, pro_shift, pro_slope, dy, dw, ws, ws_elems, sv_ngroups(groups), (hipStream_t)stream, &rc))
-            return rc;
-        // the thin 3x3 layers at 32x32 (16 input channels): the whole gradient in every block (thwgrad.hip)
-        if (use_tr && sv_thwgrad_try(g, dtype, x, pro_scale, pro_shift, pro_slope, dy, dw, sv_ngroups(groups), (hipStream_t)stream, &rc))
-            return rc;
-        // svhn_VAE's thin 4x4 stride-2 layers (first convolution, last transposed convolution): the whole gradient in every block (k4wgrad.hip)
-        if (use_tr && sv_k4wgrad_try(g, dtype, x, pro_scale, pro_shift, pro_slope, dy, dw, ws, ws_elems, sv_ngroups(groups), (hipStream_t)stream, &rc))
-            return rc;
-        // the stride-2 3x3 layer 32 -> 64: the whole gradient in every block, bands staged once (s2wgrad.hip)
-        if (use_tr && sv_s2wgrad_try(g, dtype, x, pro_scale, pro_shift, pro_slope, dy, dw, sv_ngroups(groups), (hipStream_t)stream, &rc))
-            return rc;
-        // the other layers with a spatial extent: tap-fused LDS-halo weight gradient (hwgrad.hip)
-        if (use_tr && sv_hwgrad_try(g, dtype, x, pro_scale, pro_shift, pro_slope, dy, dw, ws, ws_elems, sv_ngroups(groups), (hipStream_t)stream, &rc))
-            return rc;
-    }
+// the generic kernels: the tail of the dispatch, takes every launch
+static int wgrad_generic_try(const sv_geom* g, int dtype, const sv_wgrad_args& a, hipStream_t s, int* rc) {
+    const int use_tr = a.use_tr;
+    int splits = a.splits;
+    const int det_cap = sv_deterministic() ? det_slabs_cap(g, a.ws, a.ws_elems) : 0;
     wg_params p;
-    p.x = x; p.pro_scale = pro_scale; p.pro_shift = pro_shift; p.pro_slope = pro_slope;
-    p.dy = dy; p.dw = dw;
-    p.groups = sv_ngroups(groups);
-    p.wsh = ilog2_exact(g->Wq);
-    p.hwsh = ilog2_exact(g->Hq * g->Wq);
+    sv_wg_operands(p, a);
+    p.dw = a.dw;
+    p.groups = a.groups;
+    p.wsh = sv_ilog2_exact(g->Wq);
+    p.hwsh = sv_ilog2_exact(g->Hq * g->Wq);
     if (p.wsh < 0 || p.hwsh < 0) p.wsh = p.hwsh = -1;
     p.ntap_total = 0;
     p.incr = !sv_disabled(SV_K_WGRAD_INCR);
     p.slab_stride = 0;
     for (int i = 0; i < g->nphase; ++i) p.ntap_total += g->phase[i].ntap;
-    if (p.ntap_total == 0) return SV_OK;
+    *rc = SV_OK;
+    if (p.ntap_total == 0) return 1;
     const int64_t M = (int64_t)g->B * g->Hq * g->Wq;
     if (dtype == SV_BF16 && use_tr && splits <= 0 && !sv_disabled(SV_K_WGRAD_WIDE) && g->N % 160 == 0 && g->Cin % 160 == 0 &&
-        M * p.groups >= (int64_t)256 * sv_wide_min_blocks() && (!sv_deterministic() || det_cap))
-        return launch_c<5, 5>(g, p, M, (hipStream_t)stream, det_cap ? ws : nullptr, det_cap);
+        M * p.groups >= (int64_t)256 * sv_wide_min_blocks() && (!sv_deterministic() || det_cap)) {
+        *rc = launch_c<5, 5>(g, p, M, s, det_cap ? a.ws : nullptr, det_cap);
+        return 1;
+    }
     // tile: the widest of {64,32,16} that divides; fp32 is capped at 32 (LDS budget)
     auto pick = [&](int n) { int t = (n % 64 == 0) ? 4 : (n % 32 == 0 ? 2 : 1); if (n >= 64 && t == 1) t = (n % 32 == 0) ? 2 : 1; return t; };
     int tn = pick(g->N), tc = pick(g->Cin);
@@ -675,15 +621,74 @@ extern "C" int sv_wgrad(const sv_geom* g, int dtype, const void* x, const float*
     if (splits < 8) splits = (int)((M + m_per - 1) / m_per);
     p.splits = splits;
     p.m_per = (int)m_per;
-    hipStream_t s = (hipStream_t)stream;
     const bool slabs = det_cap && splits > 1;
-    if (slabs && !det_slabs_begin(g, p, ws, s)) return sv_check_launch("sv_wgrad: slab clear");
-    int rc;
-    if (dtype == SV_BF16) rc = use_tr ? dispatch<bf16, true>(g, p, tn, tc, s) : dispatch<bf16, false>(g, p, tn, tc, s);
-    else rc = dispatch<float, false>(g, p, tn, tc, s);
-    if (rc == SV_OK && slabs) {
-        sv_slab_reduce(ws, splits, (int64_t)g->N * g->T_orig * g->Cin, dw, s);
-        rc = sv_check_launch("sv_wgrad: slab reduce");
+    if (slabs && !det_slabs_begin(g, p, a.ws, s)) { *rc = sv_check_launch("sv_wgrad: slab clear"); return 1; }
+    if (dtype == SV_BF16) *rc = use_tr ? dispatch<bf16, true>(g, p, tn, tc, s) : dispatch<bf16, false>(g, p, tn, tc, s);
+    else *rc = dispatch<float, false>(g, p, tn, tc, s);
+    if (*rc == SV_OK && slabs) {
+        sv_slab_reduce(a.ws, splits, (int64_t)g->N * g->T_orig * g->Cin, a.dw, s);
+        *rc = sv_check_launch("sv_wgrad: slab reduce");
     }
+    return 1;
+}
+
+// one launch (deterministic mode: one group): the first candidate that takes it
+static int wgrad_launch(const sv_geom* g, int dtype, sv_wgrad_args a, hipStream_t s) {
+    // deterministic mode, generic kernels: one adder per weight -- the m ranges write slabs of their own in the caller's
+    // workspace and a fixed-order pass adds them to dw (without a workspace: a single m range)
+    if (sv_deterministic()) a.splits = det_slabs_cap(g, a.ws, a.ws_elems) ? 0 : 1;
+    int rc = 0;
+    if (dtype == SV_F32 || a.use_tr) {
+        // stride-1 3x3: LDS-halo kernels (wgrad3x3.hip) unless switched off
+        if (!sv_disabled(SV_K_WGRAD3X3) && sv_wgrad3x3_try(g, dtype, a, s, &rc)) return rc;
+        // the thin 3x3 layers at 32x32 (16 input channels): the whole gradient in every block (thwgrad.hip)
+        if (a.use_tr && sv_thwgrad_try(g, dtype, a, s, &rc)) return rc;
+        // svhn_VAE's thin 4x4 stride-2 layers (first convolution, last transposed convolution): the whole gradient in every block (k4wgrad.hip)
+        if (a.use_tr && sv_k4wgrad_try(g, dtype, a, s, &rc)) return rc;
+        // the stride-2 3x3 layer 32 -> 64: the whole gradient in every block, bands staged once (s2wgrad.hip)
+        if (a.use_tr && sv_s2wgrad_try(g, dtype, a, s, &rc)) return rc;
+        // the other layers with a spatial extent: tap-fused LDS-halo weight gradient (hwgrad.hip)
+        if (a.use_tr && sv_hwgrad_try(g, dtype, a, s, &rc)) return rc;
+    }
+    wgrad_generic_try(g, dtype, a, s, &rc);
     return rc;
+}
+
+// both entry points: the argument checks, then one launch -- or, in deterministic mode, one per group
+static int wgrad_checked(const sv_geom* g, int dtype, const sv_wgrad_args& args, void* stream) {
+    SV_REQUIRE(g && args.x && args.dy && args.dw, SV_E_ARG, "sv_wgrad: null argument");
+    SV_REQUIRE(dtype == SV_F32 || dtype == SV_BF16, SV_E_ARG, "sv_wgrad: bad dtype %d", dtype);
+    SV_REQUIRE(g->Cin % 16 == 0 && g->N % 16 == 0 && g->ldx % 8 == 0 && g->ldo % 8 == 0, SV_E_SHAPE,
+               "sv_wgrad: Cin=%d N=%d must be multiples of 16", g->Cin, g->N);
+    SV_REQUIRE(!args.pro_scale || args.pro_shift, SV_E_ARG, "sv_wgrad: prologue shift missing");
+    SV_REQUIRE(args.groups >= 0 && args.groups <= SV_MAX_GROUPS, SV_E_ARG, "sv_wgrad: groups=%d (at most %d)", args.groups, SV_MAX_GROUPS);
+    SV_REQUIRE(!args.pro_scale || (args.pro_slope >= 0.f && args.pro_slope <= 1.f), SV_E_ARG,
+               "sv_wgrad: activation slope %g outside [0, 1]", (double)args.pro_slope);
+    sv_wgrad_args a = args;
+    a.groups = sv_ngroups(args.groups);
+    if (!(sv_deterministic() && a.groups > 1)) return wgrad_launch(g, dtype, a, (hipStream_t)stream);
+    // fixed summation order: the groups of a batched launch one after the other (stream order), each a launch whose
+    // blocks add ONCE per weight (partial slabs + ordered reduction, or a single M range of the generic kernel)
+    const sv_wg_g<sv_wgrad_args> A = sv_expand_wg(*g, a, a.groups, dtype == SV_BF16 ? 2 : 4);
+    for (int grp = 0; grp < a.groups; ++grp) {
+        sv_wgrad_args one = A.g[grp];
+        one.groups = 1;
+        const int rc = wgrad_launch(g, dtype, one, (hipStream_t)stream);
+        if (rc != SV_OK) return rc;
+    }
+    return SV_OK;
+}
+
+extern "C" int sv_wgrad_ex(const sv_geom* g, int dtype, const sv_wgrad_args* a, void* stream) {
+    SV_REQUIRE(g && a, SV_E_ARG, "sv_wgrad_ex: null argument");
+    SV_REQUIRE(a->block_budget == 0 || a->block_budget >= 8, SV_E_ARG, "sv_wgrad_ex: block_budget=%d", a->block_budget);
+    SvBudgetScope budget_scope(a->block_budget);
+    return wgrad_checked(g, dtype, *a, stream);
+}
+
+extern "C" int sv_wgrad(const sv_geom* g, int dtype, const void* x, const float* pro_scale,
+                        const float* pro_shift, float pro_slope, const void* dy, float* dw, int splits,
+                        int use_tr, float* ws, int64_t ws_elems, int groups, void* stream) {
+    const sv_wgrad_args a = {x, pro_scale, pro_shift, pro_slope, dy, dw, splits, use_tr, ws, ws_elems, groups, /*block_budget*/ 0};
+    return wgrad_checked(g, dtype, a, stream);
 }

@@ -1083,14 +1083,9 @@ int launch(const sv_geom* g, const wg3_params& p, hipStream_t s) {
     constexpr int HHn = (TR < W) ? TR : W, LROWSn = TR + TR / HHn + 1;
     const size_t lds = (size_t)(128 + LROWSn * (W + 2)) * LDH * sizeof(T);
     // fp32 on 4 x 4 maps (eight spacer rows): 70 KiB of dynamic LDS needs the opt-in -- the first launch of this family that does.
-    // One flag per instantiation, as in conv3x3.hip: like the dispatcher options it assumes one device and no concurrent first calls.
-    static bool optin = false;
-    if (lds > 64 * 1024 && !optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_kernel<T, WLOG, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_kernel<T, WLOG, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(wgrad3x3)");
-        optin = true;
-    }
+    static bool optin = false;          // (both instantiations under one flag)
+    if (lds > 64 * 1024)
+        if (const int rc = sv_lds_optin(optin, (int)lds, "wgrad3x3", &wgrad3x3_kernel<T, WLOG, 1>, &wgrad3x3_kernel<T, WLOG, 2>)) return rc;
     sv_prof_begin(s);
     if (sizeof(T) == 2 && g->N * g->Cin <= 64 * 64)
         hipLaunchKernelGGL((wgrad3x3_kernel<T, WLOG, 2>), dim3(grid, p.groups), dim3(256), lds, s, *g, sv_expand_wg(*g, p, p.groups, (int)sizeof(T)));
@@ -1114,12 +1109,7 @@ int launch_m(const sv_geom* g, const wg3_params& p, hipStream_t s) {
     const int nNC = (g->N / NB) * (g->Cin / 32);
     const int grid = p.splits * nNC;
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3m_kernel<WLOG, NB>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(wgrad3x3m)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, (int)lds, "wgrad3x3m", &wgrad3x3m_kernel<WLOG, NB>)) return rc;
     auto PG = sv_expand_wg(*g, p, p.groups, 2);
     sv_prof_begin(s);
     hipLaunchKernelGGL((wgrad3x3m_kernel<WLOG, NB>), dim3(grid, p.groups), dim3(256), lds, s, *g, PG);
@@ -1139,12 +1129,7 @@ int launch_wide(const sv_geom* g, const wg3_params& p, hipStream_t s) {
     constexpr int HHc = (TR < W) ? TR : W, LROWSc = TR + TR / HHc + 1;
     const size_t lds = (size_t)(128 * LDY + LROWSc * (W + 2) * LDH + 512) * 2 * 2;      // two stages
     static bool optin = false;
-    if (!optin) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3w_kernel<WLOG>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return sv_check_launch("hipFuncSetAttribute(wgrad3x3w)");
-        optin = true;
-    }
+    if (const int rc = sv_lds_optin(optin, (int)lds, "wgrad3x3w", &wgrad3x3w_kernel<WLOG>)) return rc;
     sv_prof_begin(s);
     hipLaunchKernelGGL((wgrad3x3w_kernel<WLOG>), dim3(grid), dim3(256), lds, s, *g, sv_expand_wg(*g, p, p.groups, 2));
     sv_prof_end(s);
@@ -1160,9 +1145,7 @@ int launch_wide(const sv_geom* g, const wg3_params& p, hipStream_t s) {
 void sv_slab_reduce(const float* ws, int nslabs, int64_t n, float* dw, hipStream_t s) { launch_slab_reduce(ws, nslabs, n, dw, s); }
 
 // Returns 1 and sets *rc when the geometry is a stride-1 3x3 convolution this kernel covers.
-int sv_wgrad3x3_try(const sv_geom* g, int dtype, const void* x, const float* pro_scale, const float* pro_shift,
-                    float pro_slope, const void* dy, float* dw, float* ws, int64_t ws_elems, int groups, hipStream_t s,
-                    int* rc) {
+int sv_wgrad3x3_try(const sv_geom* g, int dtype, const sv_wgrad_args& a, hipStream_t s, int* rc) {
     if (g->nphase != 1 || g->phase[0].ntap != 9 || g->sy != 1 || g->sx != 1 || g->osy != 1 || g->osx != 1) return 0;
     if (g->Hq != g->Hin || g->Wq != g->Win || g->Hout != g->Hin || g->Wout != g->Win || g->Hin != g->Win) return 0;
     if (g->Win != 4 && g->Win != 8 && g->Win != 16 && g->Win != 32) return 0;
@@ -1174,9 +1157,10 @@ int sv_wgrad3x3_try(const sv_geom* g, int dtype, const void* x, const float* pro
     const int TR = 128 / g->Win;
     if ((g->B * g->Hin) % TR != 0) return 0;
     wg3_params p;
-    p.x = x; p.pro_scale = pro_scale; p.pro_shift = pro_shift; p.pro_slope = pro_slope; p.dy = dy; p.dw = dw;
+    sv_wg_operands(p, a);
+    p.dw = a.dw;
     p.unit = 0;
-    p.groups = groups;
+    const int groups = p.groups = a.groups;
     const int nT = g->B * g->Hin / TR;          // per group
     if (g->Win != 4 && !sv_disabled(SV_K_WGRAD3X3W) && dtype == SV_BF16 && g->N % 160 == 0 && g->Cin >= 96) {
         // wide layers: 160 x 32 slabs, one block (one wave per SIMD) per CU.  Pick the split count and the affinity unit
@@ -1198,7 +1182,7 @@ int sv_wgrad3x3_try(const sv_geom* g, int dtype, const void* x, const float* pro
         for (int sp = 1; sp <= nT && sp <= 128; ++sp) {
             const int tp = (nT + sp - 1) / sp;
             if ((nT + tp - 1) / tp != sp) continue;               // no empty splits
-            const bool fits = sp == 1 || (ws && ws_elems >= (int64_t)sp * slab_elems);
+            const bool fits = sp == 1 || (a.ws && a.ws_elems >= (int64_t)sp * slab_elems);
             for (int u = 1; u <= nC && u <= 32; ++u) {
                 if (nC % u) continue;
                 const int units = sp * nNt * (nC / u);
@@ -1216,7 +1200,7 @@ int sv_wgrad3x3_try(const sv_geom* g, int dtype, const void* x, const float* pro
         p.unit = unit;
         p.tiles_per = (nT + splits - 1) / splits;
         const int64_t needw = (int64_t)splits * g->N * g->T_orig * g->Cin;
-        p.ws = (ws && ws_elems >= needw && splits > 1) ? ws : nullptr;
+        p.ws = (a.ws && a.ws_elems >= needw && splits > 1) ? a.ws : nullptr;
         if (!p.ws && splits > 1 && sv_deterministic()) return 0;      // (the splits would meet in dw through float atomics)
         switch (g->Win) {
             case 32: *rc = launch_wide<5>(g, p, s); break;
@@ -1241,7 +1225,7 @@ int sv_wgrad3x3_try(const sv_geom* g, int dtype, const void* x, const float* pro
     if (splits < 8) splits = (nT + p.tiles_per - 1) / p.tiles_per;
     p.splits = splits;
     const int64_t need = (int64_t)splits * groups * g->N * g->T_orig * g->Cin;
-    p.ws = (ws && ws_elems >= need && splits * groups > 1) ? ws : nullptr;    // no workspace: atomics straight into dw
+    p.ws = (a.ws && a.ws_elems >= need && splits * groups > 1) ? a.ws : nullptr;    // no workspace: atomics straight into dw
     if (!p.ws && splits * groups > 1 && sv_deterministic()) return 0;
     if (use_m) {
         switch (g->Win) {
