@@ -148,56 +148,31 @@ __device__ __forceinline__ void sv_bn_moments(double s1, double s2, float count,
     var = (float)v;
     rs = rsqrtf(var + eps);
 }
+// <256, false>: the form above.  <512, true>: the 512-thread kernels with register-resident weights (tconv.hip, sconv.hip),
+// C = 32 / 64 / 128 channels (C divides 512: every thread has a part), the coefficients as [C] pairs {scale, shift} in LDS
+// (sc_out = the pairs, sh_out = sc_out + 1); `scratch`: 2 * 512 doubles of LDS (8 KB).
+template <int THREADS, bool PAIRS>
 __device__ __forceinline__ void sv_bn_fold_block(const sv_igemm_args& a, int C, double* scratch, float* sc_out, float* sh_out,
                                                  bool writer) {
-    const int tid = threadIdx.x, c = tid % C, part = tid / C, parts = 256 / C;
+    constexpr int S = PAIRS ? 2 : 1;
+    const int tid = threadIdx.x, c = tid % C, part = tid / C, parts = THREADS / C;
     double s1 = 0.0, s2 = 0.0;
-    if (part < parts)
+    if (PAIRS || part < parts)
         for (int r = part; r < a.fold_replicas; r += parts) {
             s1 += a.fold_stats[(size_t)r * 2 * C + c];
             s2 += a.fold_stats[(size_t)r * 2 * C + C + c];
         }
     scratch[tid] = s1;
-    scratch[256 + tid] = s2;
+    scratch[THREADS + tid] = s2;
     __syncthreads();
     if (tid < C) {
         double t1 = 0.0, t2 = 0.0;
-        for (int q = 0; q < parts; ++q) { t1 += scratch[q * C + tid]; t2 += scratch[256 + q * C + tid]; }
+        for (int q = 0; q < parts; ++q) { t1 += scratch[q * C + tid]; t2 += scratch[THREADS + q * C + tid]; }
         float mu, var, rs;
         sv_bn_moments(t1, t2, a.fold_count, a.fold_eps, mu, var, rs);
         const float sc = a.fold_gamma[tid] * rs, sh = a.fold_beta[tid] - mu * sc;
-        sc_out[tid] = sc;
-        sh_out[tid] = sh;
-        if (writer) {
-            const_cast<float*>(a.pro_scale)[tid] = sc;
-            const_cast<float*>(a.pro_shift)[tid] = sh;
-            a.fold_mean[tid] = mu;
-            a.fold_rstd[tid] = rs;
-        }
-    }
-    __syncthreads();
-}
-
-// The same for the 512-thread kernels with register-resident weights (tconv.hip, sconv.hip): C = 32 / 64 / 128 channels, the
-// coefficients as [C] pairs {scale, shift} (coef2, LDS).  `scratch`: 2 * 512 doubles of LDS (8 KB).  Ends with a barrier.
-__device__ __forceinline__ void sv_bn_fold_block512(const sv_igemm_args& a, int C, double* scratch, float* coef2, bool writer) {
-    const int tid = threadIdx.x, c = tid % C, part = tid / C, parts = 512 / C;
-    double s1 = 0.0, s2 = 0.0;
-    for (int r = part; r < a.fold_replicas; r += parts) {
-        s1 += a.fold_stats[(size_t)r * 2 * C + c];
-        s2 += a.fold_stats[(size_t)r * 2 * C + C + c];
-    }
-    scratch[tid] = s1;
-    scratch[512 + tid] = s2;
-    __syncthreads();
-    if (tid < C) {
-        double t1 = 0.0, t2 = 0.0;
-        for (int q = 0; q < parts; ++q) { t1 += scratch[q * C + tid]; t2 += scratch[512 + q * C + tid]; }
-        float mu, var, rs;
-        sv_bn_moments(t1, t2, a.fold_count, a.fold_eps, mu, var, rs);
-        const float sc = a.fold_gamma[tid] * rs, sh = a.fold_beta[tid] - mu * sc;
-        coef2[2 * tid] = sc;
-        coef2[2 * tid + 1] = sh;
+        sc_out[S * tid] = sc;
+        sh_out[S * tid] = sh;
         if (writer) {
             const_cast<float*>(a.pro_scale)[tid] = sc;
             const_cast<float*>(a.pro_shift)[tid] = sh;
@@ -276,7 +251,7 @@ bool sv_deterministic();               // sv_set_option(SV_OPT_DETERMINISTIC, 1)
 bool sv_det_stats();                   // ... 1 or 2: the BatchNorm statistics / backward sums in a fixed order (2: only those)
 float* sv_det_scratch(size_t floats);  // deterministic mode: a slice of the library's scratch ring (nullptr + error text on failure)
 enum { SV_FLAG_DET = 1 };              // sv_igemm_args::flags
-// sv_igemm_query_blocks: the launch functions call sv_dry_run(grid) right before their launch; it returns true (and records
+// sv_igemm_query_blocks: sv_igemm_launch calls sv_dry_run(grid) right before its launch; it returns true (and records
 // the grid) when the calling thread is inside a query -- the caller then returns SV_OK without launching.  In deterministic
 // mode it also checks the replica count of a real launch (returns true with *rc < 0 when it is too small).
 bool sv_dry_run(int grid_x, const sv_igemm_args* a, int* rc);
@@ -292,11 +267,6 @@ __device__ __forceinline__ void sv_start_signal(const sv_igemm_args& a) {
     if (a.start_flag && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
         __hip_atomic_store(a.start_flag, a.start_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-#define SV_LAUNCH_GATE(grid_x, a)                                \
-    do {                                                         \
-        int gate_rc_ = SV_OK;                                    \
-        if (sv_dry_run((grid_x), (a), &gate_rc_)) return gate_rc_; \
-    } while (0)
 int sv_check_launch(const char* what);
 void sv_prof_begin(hipStream_t s);
 void sv_prof_end(hipStream_t s);
@@ -306,6 +276,25 @@ struct SvProfScope {
     explicit SvProfScope(void* st) : s((hipStream_t)st) { sv_prof_begin(s); }
     ~SvProfScope() { sv_prof_end(s); }
 };
+// The argument block a launcher's kernel gets: *a, with fold_stats kept only if the launcher claims the pending fold.
+inline sv_igemm_args sv_fold_resolve(const sv_igemm_args& a, bool can) {
+    sv_igemm_args b = a;
+    if (!sv_fold_claim(can)) b.fold_stats = nullptr;
+    return b;
+}
+// The one launch path of the sv_igemm family: the gate (sv_dry_run -- a grid query, the deterministic replica check and the
+// materialisation of an unclaimed fold; its rc is returned when nothing is to be launched), then `kernel` on grid_x x groups
+// blocks of `threads` threads with (*g, the per-group argument blocks, extra...).  `es`: the element size of x / out.
+template <typename K, typename... X>
+inline int sv_igemm_launch(K* kernel, int grid_x, int threads, size_t lds, const sv_geom* g, const sv_igemm_args* a, int es,
+                           hipStream_t s, const char* label, X... extra) {
+    int rc = SV_OK;
+    if (sv_dry_run(grid_x, a, &rc)) return rc;
+    sv_prof_begin(s);
+    hipLaunchKernelGGL(kernel, dim3(grid_x, sv_ngroups(a->groups)), dim3(threads), lds, s, *g, sv_expand_groups(*g, *a, es), extra...);
+    sv_prof_end(s);
+    return sv_check_launch(label);
+}
 // Raises the dynamic-LDS limit of `kernels` (more than 64 KiB per block needs the opt-in; gfx950 has 160 KiB per CU) to `bytes`,
 // once per call site: `done` is the site's own `static bool`, one per kernel instantiation; after the first call this is that
 // flag's test and nothing else.  A failure is reported through sv_check_launch as "hipFuncSetAttribute(<name>)".
@@ -336,14 +325,10 @@ inline int sv_block_slots(int n, int per) {
 }
 // adds `nslabs` partial slabs of n floats (plain stores of a weight-gradient kernel, in ws) to dw in a fixed order (wgrad3x3.hip)
 void sv_slab_reduce(const float* ws, int nslabs, int64_t n, float* dw, hipStream_t s);
-int sv_conv3x3_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
-int sv_halo_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
-int sv_tconvr_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
-int sv_sconv_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
-int sv_pconv_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
-int sv_dconv_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
-int sv_thconv_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
-int sv_conv3x3w_try(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
+// The specialised candidates of sv_igemm (igemm.hip, whose generic kernels are its tail): each returns 1 and sets *rc when it
+// takes the launch.  (sv_conv3x3_try tries sv_conv3x3w_try first, which tries sv_conv3x3x_try.)
+typedef int sv_igemm_try_fn(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
+sv_igemm_try_fn sv_conv3x3_try, sv_halo_try, sv_tconvr_try, sv_sconv_try, sv_pconv_try, sv_dconv_try, sv_thconv_try, sv_conv3x3w_try;
 int sv_conv3x3x_try(const sv_geom* g, const sv_igemm_args* a, bool fwd, hipStream_t s, int* rc);
 // The specialised candidates of the weight-gradient dispatch (wgrad.hip, whose generic kernels are its tail with the same
 // signature), in its order: each returns 1 and sets *rc when it takes the launch.  `a` is the checked operand block with

@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256, SV_C3P_WAVES) void conv3x3p_kernel(const sv_ge
         // statistics itself (sv_igemm_args::fold_*; the halo area is free until the first tile is stored), the first block
         // of the launch also stores them for the backward pass
         float* fs = reinterpret_cast<float*>(halo);
-        sv_bn_fold_block(a, CIN, reinterpret_cast<double*>(halo), fs + 1024, fs + 1024 + CIN, blockIdx.x == 0);
+        sv_bn_fold_block<256, false>(a, CIN, reinterpret_cast<double*>(halo), fs + 1024, fs + 1024 + CIN, blockIdx.x == 0);
         ps0 = *reinterpret_cast<const f32x4*>(fs + 1024 + hc[0]);
         ps1 = *reinterpret_cast<const f32x4*>(fs + 1024 + hc[0] + 4);
         pt0 = *reinterpret_cast<const f32x4*>(fs + 1024 + CIN + hc[0]);
@@ -745,11 +745,7 @@ int launch_m(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     static bool optin = false;
     if (lds > 64 * 1024)
         if (const int rc = sv_lds_optin(optin, (int)lds, "conv3x3m", &conv3x3m_kernel<T, NT, WLOG, PT>)) return rc;
-    SV_LAUNCH_GATE(grid, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((conv3x3m_kernel<T, NT, WLOG, PT>), dim3(grid, sv_ngroups(a->groups)), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, (int)sizeof(T)));
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(conv3x3m)");
+    return sv_igemm_launch(&conv3x3m_kernel<T, NT, WLOG, PT>, grid, 256, lds, g, a, (int)sizeof(T), s, "sv_igemm(conv3x3m)");
 }
 
 template <typename T, int NT, int PT>
@@ -779,14 +775,9 @@ int launch_pm(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     static bool optin = false;
     if (lds > 64 * 1024)
         if (const int rc = sv_lds_optin(optin, (int)lds, "conv3x3p", &conv3x3p_kernel<T, WLOG, CCH, MODE>)) return rc;
-    sv_igemm_args b = *a;          // this kernel folds the BatchNorm finalisation of its prologue (<= 64 channels, <= 64 replicas)
-    if (!sv_fold_claim(b.fold_stats && b.fold_replicas <= 64 && (size_t)HPIX * LDW * sizeof(T) >= (size_t)(1024 + 2 * CIN) * 4)) b.fold_stats = nullptr;
-    a = &b;
-    SV_LAUNCH_GATE(chunks * nNt, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((conv3x3p_kernel<T, WLOG, CCH, MODE>), dim3(chunks * nNt, sv_ngroups(a->groups)), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, (int)sizeof(T)), tiles_per);
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(conv3x3p)");
+    // this kernel folds the BatchNorm finalisation of its prologue (<= 64 channels, <= 64 replicas)
+    const sv_igemm_args b = sv_fold_resolve(*a, a->fold_stats && a->fold_replicas <= 64 && (size_t)HPIX * LDW * sizeof(T) >= (size_t)(1024 + 2 * CIN) * 4);
+    return sv_igemm_launch(&conv3x3p_kernel<T, WLOG, CCH, MODE>, chunks * nNt, 256, lds, g, &b, (int)sizeof(T), s, "sv_igemm(conv3x3p)", tiles_per);
 }
 
 // the three launch kinds of the training step take the binaries with their fusion flags at compile time (bf16 only)
@@ -820,11 +811,7 @@ int launch(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     static bool optin = false;          // > 64 KiB of dynamic LDS needs an opt-in (gfx950 has 160 KiB per CU)
     if (lds > 64 * 1024)
         if (const int rc = sv_lds_optin(optin, (int)lds, "conv3x3", &conv3x3_kernel<T, NT, WLOG>)) return rc;
-    SV_LAUNCH_GATE(grid, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((conv3x3_kernel<T, NT, WLOG>), dim3(grid, sv_ngroups(a->groups)), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, (int)sizeof(T)));
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(conv3x3)");
+    return sv_igemm_launch(&conv3x3_kernel<T, NT, WLOG>, grid, 256, lds, g, a, (int)sizeof(T), s, "sv_igemm(conv3x3)");
 }
 
 template <typename T, int NT>

@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3w_kernel(const sv_geom g, const
         // below read them (the halo buffers are free until the first DMA; the block's stores and its later loads take the
         // same path through the CU's vector cache to L2, in order)
         float* fs = reinterpret_cast<float*>(smem);
-        sv_bn_fold_block(a, Cin, reinterpret_cast<double*>(smem), fs + 1024, fs + 1024 + Cin, true);
+        sv_bn_fold_block<256, false>(a, Cin, reinterpret_cast<double*>(smem), fs + 1024, fs + 1024 + Cin, true);
         __threadfence_block();
     }
     __syncthreads();                                   // ssum / identity coefficients visible (no DMA in flight yet)
@@ -382,15 +382,9 @@ int launch_w4(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     static bool optin = false;
     if (const int rc = sv_lds_optin(optin, (int)lds, "conv3x3w", &conv3x3w_kernel<NF, WLOG, REV, MODE>)) return rc;
     // BatchNorm finalisation folded into this launch: the blocks sum the replicas themselves (256 threads = 256 / Cin parts)
-    sv_igemm_args b = *a;
-    if (!sv_fold_claim(b.fold_stats && 256 % g->Cin == 0 && b.fold_replicas <= 64 && (size_t)(1024 + 2 * g->Cin) * 4 <= (size_t)C::HB))
-        b.fold_stats = nullptr;
-    a = &b;
-    SV_LAUNCH_GATE(grid, a);          // (deterministic mode: a replica per block -- the gate checks replicas >= 4 * grid)
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((conv3x3w_kernel<NF, WLOG, REV, MODE>), dim3(grid, sv_ngroups(a->groups)), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, 2));
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(conv3x3w)");
+    const sv_igemm_args b = sv_fold_resolve(*a, a->fold_stats && 256 % g->Cin == 0 && a->fold_replicas <= 64 && (size_t)(1024 + 2 * g->Cin) * 4 <= (size_t)C::HB);
+    // (deterministic mode: a replica per block -- the gate checks replicas >= 4 * grid)
+    return sv_igemm_launch(&conv3x3w_kernel<NF, WLOG, REV, MODE>, grid, 256, lds, g, &b, 2, s, "sv_igemm(conv3x3w)");
 }
 
 // the 128-channel tiles at 8 x 8 (the last stage of WRN-28-2, 14 launches per step) take the binaries with their fusion flags

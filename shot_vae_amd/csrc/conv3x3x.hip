@@ -654,11 +654,8 @@ int launch_x4(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const size_t lds = (size_t)C::LDS;
     static bool optin = false;
     if (const int rc = sv_lds_optin(optin, (int)lds, "conv3x3x", &conv3x3x_kernel<WLOG, REV, MODE, DMAH>)) return rc;
-    SV_LAUNCH_GATE(grid, a);          // (deterministic mode: a replica per block -- the gate checks replicas >= 4 * grid)
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((conv3x3x_kernel<WLOG, REV, MODE, DMAH>), dim3(grid, G), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, 2));
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(conv3x3x)");
+    // (deterministic mode: a replica per block -- the gate checks replicas >= 4 * grid)
+    return sv_igemm_launch(&conv3x3x_kernel<WLOG, REV, MODE, DMAH>, grid, 256, lds, g, a, 2, s, "sv_igemm(conv3x3x)");
 }
 
 // forward launches come with statistics (+ residual), data gradients with the activation-backward epilogue; anything else

@@ -235,12 +235,7 @@ int launch_dconv(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const int grid = sv_block_slots(nband, sv_persistent_blocks() / 2 / G);      // (the budget counts two blocks per CU; this kernel is one)
     static bool optin = false;
     if (const int rc = sv_lds_optin(optin, C::LDS, "dconv", &dconv_kernel<NOUT_, EX_>)) return rc;
-    int gate_rc = SV_OK;
-    if (sv_dry_run(grid, a, &gate_rc)) return gate_rc;
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((dconv_kernel<NOUT_, EX_>), dim3(grid, G), dim3(C::NTH), C::LDS, s, *g, sv_expand_groups(*g, *a, 2));
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(dconv)");
+    return sv_igemm_launch(&dconv_kernel<NOUT_, EX_>, grid, C::NTH, C::LDS, g, a, 2, s, "sv_igemm(dconv)");
 }
 
 }  // namespace

@@ -518,7 +518,7 @@ __global__ __launch_bounds__(256, OCC) void halop_kernel(const sv_geom g, const 
         // tile is stored --, the first block of the launch stores them for the backward pass
         const int cv8 = 8 * (tid % VPP);
         float* fs = reinterpret_cast<float*>(halo);
-        sv_bn_fold_block(a, Cin, reinterpret_cast<double*>(halo), fs + 1024, fs + 1024 + Cin, blockIdx.x == 0);
+        sv_bn_fold_block<256, false>(a, Cin, reinterpret_cast<double*>(halo), fs + 1024, fs + 1024 + Cin, blockIdx.x == 0);
         ps0 = *reinterpret_cast<const f32x4*>(fs + 1024 + cv8);
         ps1 = *reinterpret_cast<const f32x4*>(fs + 1024 + cv8 + 4);
         pt0 = *reinterpret_cast<const f32x4*>(fs + 1024 + Cin + cv8);
@@ -722,16 +722,9 @@ int launch_halop_pv(const sv_geom* g, const sv_igemm_args* a, const halo_cfg& c,
     static bool optin = false;
     if (lds > 64 * 1024)
         if (const int rc = sv_lds_optin(optin, 160 * 1024, "halop", &halop_kernel<T, NT, CC, NPH, PV, OCC, MODE>)) return rc;
-    sv_igemm_args b = *a;          // the persistent kernel folds the BatchNorm finalisation of its prologue (fold_*)
-    if (!sv_fold_claim(b.fold_stats && b.fold_replicas <= 64 && 256 % g->Cin == 0 && (size_t)c.HP * (g->Cin + 16) * sizeof(T) >= (1024 + 2 * 64) * 4))
-        b.fold_stats = nullptr;
-    a = &b;
-    SV_LAUNCH_GATE(chunks * nNt, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((halop_kernel<T, NT, CC, NPH, PV, OCC, MODE>), dim3(chunks * nNt, sv_ngroups(a->groups)), dim3(256), lds, s, *g,
-                       sv_expand_groups(*g, *a, (int)sizeof(T)), c, tiles_per);
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(halop)");
+    // the persistent kernel folds the BatchNorm finalisation of its prologue (fold_*)
+    const sv_igemm_args b = sv_fold_resolve(*a, a->fold_stats && a->fold_replicas <= 64 && 256 % g->Cin == 0 && (size_t)c.HP * (g->Cin + 16) * sizeof(T) >= (1024 + 2 * 64) * 4);
+    return sv_igemm_launch(&halop_kernel<T, NT, CC, NPH, PV, OCC, MODE>, chunks * nNt, 256, lds, g, &b, (int)sizeof(T), s, "sv_igemm(halop)", c, tiles_per);
 }
 
 template <typename T, int NT, int CC, int NPH, int MODE>
@@ -786,12 +779,7 @@ int launch_halo(const sv_geom* g, const sv_igemm_args* a, const halo_cfg& c, hip
     static bool optin = false;
     if (lds > 64 * 1024)
         if (const int rc = sv_lds_optin(optin, 160 * 1024, "halo", &halo_kernel<T, NT, CC, NPH>)) return rc;
-    SV_LAUNCH_GATE(grid, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((halo_kernel<T, NT, CC, NPH>), dim3(grid, sv_ngroups(a->groups)), dim3(256), lds, s, *g,
-                       sv_expand_groups(*g, *a, (int)sizeof(T)), c);
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(halo)");
+    return sv_igemm_launch(&halo_kernel<T, NT, CC, NPH>, grid, 256, lds, g, a, (int)sizeof(T), s, "sv_igemm(halo)", c);
 }
 
 template <typename T, int CC, int NPH>

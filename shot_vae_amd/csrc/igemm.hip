@@ -527,11 +527,7 @@ int launch_dma(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     static bool optin = false;
     if (lds > 64 * 1024)
         if (const int rc = sv_lds_optin(optin, (int)lds, "igemm_dma", &igemm_dma_kernel<NT, MS>)) return rc;
-    SV_LAUNCH_GATE(grid, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((igemm_dma_kernel<NT, MS>), dim3(grid, sv_ngroups(a->groups)), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, 2));
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(dma)");
+    return sv_igemm_launch(&igemm_dma_kernel<NT, MS>, grid, 256, lds, g, a, 2, s, "sv_igemm(dma)");
 }
 
 template <typename T, int NT, int KV, int MS, bool AL>
@@ -545,11 +541,7 @@ int launch_al(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     static bool optin = false;
     if (lds > 64 * 1024)
         if (const int rc = sv_lds_optin(optin, (int)lds, "igemm", &igemm_kernel<T, NT, KV, MS, AL>)) return rc;
-    SV_LAUNCH_GATE(grid, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((igemm_kernel<T, NT, KV, MS, AL>), dim3(grid, sv_ngroups(a->groups)), dim3(256), lds, s, *g, sv_expand_groups(*g, *a, (int)sizeof(T)));
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm");
+    return sv_igemm_launch(&igemm_kernel<T, NT, KV, MS, AL>, grid, 256, lds, g, a, (int)sizeof(T), s, "sv_igemm");
 }
 
 template <typename T, int NT, int KV, int MS = 2>

@@ -28,7 +28,7 @@ __global__ __launch_bounds__(256) void pconv_kernel(const sv_geom g, const sv_ig
     bf16* __restrict__ O = reinterpret_cast<bf16*>(a.out);
     // ---- prologue coefficients (channels 16 ks + 8 h + j of this lane), folded finalisation first
     const bool has_pro = a.pro_scale != nullptr;
-    if (a.fold_stats) sv_bn_fold_block(a, CIN, fold_scratch, sc_lds, sh_lds, blockIdx.x == 0);
+    if (a.fold_stats) sv_bn_fold_block<256, false>(a, CIN, fold_scratch, sc_lds, sh_lds, blockIdx.x == 0);
     float cs[KS][8], ct[KS][8];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
@@ -122,14 +122,9 @@ int launch_pconv(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     int grid = 256 * 8 / G;                         // ~8 blocks of 4 waves per CU over the batched launch
     if (grid > (ntiles + 3) / 4) grid = (ntiles + 3) / 4;
     if (grid < 1) grid = 1;
-    sv_igemm_args b = *a;                           // folds the BatchNorm finalisation of its prologue (<= 64 channels, <= 64 replicas)
-    if (!sv_fold_claim(b.fold_stats && b.fold_replicas <= 64)) b.fold_stats = nullptr;
-    a = &b;
-    SV_LAUNCH_GATE(grid, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((pconv_kernel<CIN, NOUT>), dim3(grid, G), dim3(256), 0, s, *g, sv_expand_groups(*g, *a, 2), ntiles);
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(pconv)");
+    // folds the BatchNorm finalisation of its prologue (<= 64 channels, <= 64 replicas)
+    const sv_igemm_args b = sv_fold_resolve(*a, a->fold_stats && a->fold_replicas <= 64);
+    return sv_igemm_launch(&pconv_kernel<CIN, NOUT>, grid, 256, 0, g, &b, 2, s, "sv_igemm(pconv)", ntiles);
 }
 
 }  // namespace

@@ -123,7 +123,7 @@ __global__ __launch_bounds__(512, 1) void sconv_kernel(const sv_geom g, const sv
     }
     // (BatchNorm finalisation folded into this launch -- sv_igemm_args::fold_*: every block derives the coefficients itself, block 0
     //  of a group stores the four vectors; the scratch lies in the image area, zeroed below)
-    if (a.fold_stats) sv_bn_fold_block512(a, CIN, reinterpret_cast<double*>(smem), coef, blockIdx.x == 0);
+    if (a.fold_stats) sv_bn_fold_block<512, true>(a, CIN, reinterpret_cast<double*>(smem), coef, coef + 1, blockIdx.x == 0);
     else if (has_pro && tid < 2 * CIN) coef[tid] = (tid & 1) ? a.pro_shift[tid >> 1] : a.pro_scale[tid >> 1];
     {
         bf16x8 z;
@@ -298,14 +298,8 @@ int launch_sconv(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const int grid = sv_block_slots(nband, sv_persistent_blocks() / 2 / G);      // (the budget counts two blocks per CU; this kernel is one)
     static bool optin = false;
     if (const int rc = sv_lds_optin(optin, C::LDS, "sconv", &sconv_kernel<CIN, NOUT, W>)) return rc;
-    sv_igemm_args b = *a;          // this kernel folds the BatchNorm finalisation of its prologue
-    if (!sv_fold_claim(b.fold_stats != nullptr)) b.fold_stats = nullptr;
-    a = &b;
-    SV_LAUNCH_GATE(grid, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((sconv_kernel<CIN, NOUT, W>), dim3(grid, G), dim3(C::NTH), C::LDS, s, *g, sv_expand_groups(*g, *a, 2));
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(sconv)");
+    const sv_igemm_args b = sv_fold_resolve(*a, a->fold_stats != nullptr);      // this kernel folds the BatchNorm finalisation of its prologue
+    return sv_igemm_launch(&sconv_kernel<CIN, NOUT, W>, grid, C::NTH, C::LDS, g, &b, 2, s, "sv_igemm(sconv)");
 }
 
 }  // namespace

@@ -1777,6 +1777,13 @@ inline int nblocks(int64_t n, int bs, int cap = 2048) {
         else { sv_set_error("bad dtype %d", (int)(dtype)); return SV_E_ARG; } \
     } while (0)
 
+// one instantiation pair of bn_bwd_apply_kernel, on `nthr` threads (REG) or 256
+template <bool REG, bool DROP>
+static int bnb_launch(int dtype, dim3 grid, int nthr, size_t lds, hipStream_t s, const bnb_params_g& A) {
+    DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, REG, DROP>), grid, dim3(REG ? nthr : 256), lds, s, A));
+    return sv_check_launch(DROP ? "sv_bn_bwd_apply_dropout" : "sv_bn_bwd_apply");
+}
+
 extern "C" {
 
 int sv_bn_finalize(const double* stats, int replicas, int C, float count, const float* gamma, const float* beta, float eps,
@@ -1877,19 +1884,18 @@ static int bn_bwd_apply_launch(int dtype, int64_t M, int C, int ld, const void* 
         occ_lds = o;
         (void)hipGetLastError();
     }
-    const int cv_ = C / 8;
-    const bool reg_ = (256 % cv_ == 0 ? 256 : (cv_ <= 256 ? 256 / cv_ * cv_ : 0)) >= 192;
-    const int resident = 256 * (reg_ ? occ_reg : occ_lds);
-    const int grid = nblocks(M * (C / 8), 256, resident / groups > 64 ? resident / groups : 64);
-    const size_t lds = ((size_t)(2 + 3 * nbranch) * C + (size_t)nbranch * 2 * 256 * 2) * sizeof(float);      // (the partial sums are doubles)
-    SV_REQUIRE(lds <= 64 * 1024, SV_E_SHAPE, "sv_bn_bwd_apply: C=%d too large", C);
-    const int cv = C / 8;
     // every thread keeps one 8-channel group (coefficients in registers) when the block size is a multiple of C/8: 256
     // threads for the power-of-two widths, 240 for the 160 / 320 / 640-channel tensors of WRN-28-10 (C/8 = 20, 40, 80) -- those
-    // took the LDS-coefficient path at 3.5 TB/s
+    // took the LDS-coefficient path at 3.5 TB/s.  (Such a block covers a whole row: nthr >= 192 implies nthr >= C/8.)
+    const int cv = C / 8;
     const int nthr = 256 % cv == 0 ? 256 : (cv <= 256 ? 256 / cv * cv : 0);
-    const bool reg = nthr >= 192 && (int64_t)grid * nthr >= cv;
-    if (sv_det_stats()) {
+    const bool reg = nthr >= 192;
+    const int resident = 256 * (reg ? occ_reg : occ_lds);
+    const int grid = nblocks(M * cv, 256, resident / groups > 64 ? resident / groups : 64);
+    const size_t lds = ((size_t)(2 + 3 * nbranch) * C + (size_t)nbranch * 2 * 256 * 2) * sizeof(float);      // (the partial sums are doubles)
+    SV_REQUIRE(lds <= 64 * 1024, SV_E_SHAPE, "sv_bn_bwd_apply: C=%d too large", C);
+    const bool det = sv_det_stats();
+    if (det) {
         // dgamma / dbeta receive ONE add per launch: block (0, 0) walks the groups in index order (mode 1 only).  The accumulators
         // of these modes hold a replica per producer wave: a pre-pass folds them 256 : 1 (in order) so that the blocks of the apply
         // kernel do not each walk thousands of rows
@@ -1904,33 +1910,15 @@ static int bn_bwd_apply_launch(int dtype, int64_t M, int C, int ld, const void* 
             p.br[k].bsums = w;
             p.br[k].replicas = R2;
         }
-        bnb_params_g A;
-        DISPATCH_T(dtype, A = bnb_expand(p, groups, (int)sizeof(T)));
-        A.det_groups = sv_deterministic() ? groups : 0;
-        if (drop) {
-            A.drop = *drop;
-            if (reg) DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true>), dim3(grid, groups), dim3(nthr), lds, (hipStream_t)stream, A));
-            else DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, true>), dim3(grid, groups), dim3(256), lds, (hipStream_t)stream, A));
-            return sv_check_launch("sv_bn_bwd_apply_dropout");
-        }
-        if (reg) DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), dim3(grid, groups), dim3(nthr), lds, (hipStream_t)stream, A));
-        else DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false>), dim3(grid, groups), dim3(256), lds, (hipStream_t)stream, A));
-        return sv_check_launch("sv_bn_bwd_apply");
     }
-    if (drop) {
-        bnb_params_g A;
-        DISPATCH_T(dtype, A = bnb_expand(p, groups, (int)sizeof(T)));
-        A.drop = *drop;
-        if (reg) DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true>), dim3(grid, groups), dim3(nthr), lds, (hipStream_t)stream, A));
-        else DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, true>), dim3(grid, groups), dim3(256), lds, (hipStream_t)stream, A));
-        return sv_check_launch("sv_bn_bwd_apply_dropout");
-    }
-    if (reg) {
-        DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true>), dim3(grid, groups), dim3(nthr), lds, (hipStream_t)stream, bnb_expand(p, groups, (int)sizeof(T))));
-    } else {
-        DISPATCH_T(dtype, hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false>), dim3(grid, groups), dim3(256), lds, (hipStream_t)stream, bnb_expand(p, groups, (int)sizeof(T))));
-    }
-    return sv_check_launch("sv_bn_bwd_apply");
+    bnb_params_g A;
+    DISPATCH_T(dtype, A = bnb_expand(p, groups, (int)sizeof(T)));
+    if (det && sv_deterministic()) A.det_groups = groups;
+    if (drop) A.drop = *drop;
+    const dim3 blocks(grid, groups);
+    hipStream_t s = (hipStream_t)stream;
+    if (drop) return reg ? bnb_launch<true, true>(dtype, blocks, nthr, lds, s, A) : bnb_launch<false, true>(dtype, blocks, nthr, lds, s, A);
+    return reg ? bnb_launch<true, false>(dtype, blocks, nthr, lds, s, A) : bnb_launch<false, false>(dtype, blocks, nthr, lds, s, A);
 }
 
 int sv_bn_bwd_apply(int dtype, int64_t M, int C, int ld, const void* x, const float* mean, const float* rstd,
@@ -2005,27 +1993,32 @@ int sv_colsum(int dtype, const void* y, int64_t M, int N, int ld, float* out, vo
     return sv_check_launch("sv_colsum");
 }
 
+// pool_fwd8_kernel / pool_bwd8_kernel (8-channel vectors): P row parts per image, ipb images of one group per 256-thread block;
+// false when the shape is not theirs
+static bool pool8_shape(int Bg, int HW, int C, int ld, int& P, int& ipb) {
+    const int cv = C / 8;
+    P = POOL_PARTS;
+    while (P > 1 && cv * P > 256) P >>= 1;
+    ipb = 256 / (cv * P) > 0 ? 256 / (cv * P) : 1;
+    return C % 8 == 0 && ld % 8 == 0 && cv <= 256 && Bg % ipb == 0 && HW >= P;
+}
+
 int sv_pool_fwd(int dtype, const void* x, const float* scale, const float* shift, float slope, int B, int HW,
                 int C, int ld, float* feat, int groups, void* stream) {
     SvProfScope prof_scope(stream);
     SV_REQUIRE(x && scale && shift && feat, SV_E_ARG, "sv_pool_fwd: null");
     SV_REQUIRE(B % sv_ngroups(groups) == 0, SV_E_ARG, "sv_pool_fwd: B=%d is not a multiple of groups=%d", B, groups);
     SV_REQUIRE(slope >= 0.f && slope <= 1.f, SV_E_ARG, "sv_pool_fwd: activation slope %g outside [0, 1]", (double)slope);
-    {
-        const int Bg = B / sv_ngroups(groups), cv = C / 8;
-        int P = POOL_PARTS;
-        while (P > 1 && cv * P > 256) P >>= 1;
-        const int ipb = 256 / (cv * P) > 0 ? 256 / (cv * P) : 1;
-        if (C % 8 == 0 && ld % 8 == 0 && cv <= 256 && Bg % ipb == 0 && HW >= P) {
-            const size_t lds = (size_t)ipb * P * C * sizeof(float);
-            DISPATCH_T(dtype, hipLaunchKernelGGL((pool_fwd8_kernel<T>), dim3((B + ipb - 1) / ipb), dim3(256), lds, (hipStream_t)stream,
-                                                 (const T*)x, scale, shift, slope, B, HW, C, ld, feat, Bg, P));
-            return sv_check_launch("sv_pool_fwd");
-        }
+    const int Bg = B / sv_ngroups(groups);
+    int P, ipb;
+    if (pool8_shape(Bg, HW, C, ld, P, ipb)) {
+        const size_t lds = (size_t)ipb * P * C * sizeof(float);
+        DISPATCH_T(dtype, hipLaunchKernelGGL((pool_fwd8_kernel<T>), dim3((B + ipb - 1) / ipb), dim3(256), lds, (hipStream_t)stream,
+                                             (const T*)x, scale, shift, slope, B, HW, C, ld, feat, Bg, P));
+        return sv_check_launch("sv_pool_fwd");
     }
     DISPATCH_T(dtype, hipLaunchKernelGGL((pool_fwd_kernel<T>), dim3((B * C + 255) / 256), dim3(256), 0,
-                                         (hipStream_t)stream, (const T*)x, scale, shift, slope, B, HW, C, ld, feat,
-                                         B / sv_ngroups(groups)));
+                                         (hipStream_t)stream, (const T*)x, scale, shift, slope, B, HW, C, ld, feat, Bg));
     return sv_check_launch("sv_pool_fwd");
 }
 
@@ -2048,21 +2041,17 @@ int sv_pool_bwd(int dtype, const void* x, const float* scale, const float* shift
         det_collect(w, P, 2 * C, G, bsums, (hipStream_t)stream);
         return sv_check_launch("sv_pool_bwd");
     }
-    {
-        const int Bg = B / sv_ngroups(groups), cv = C / 8;
-        int P = POOL_PARTS;
-        while (P > 1 && cv * P > 256) P >>= 1;
-        const int ipb = 256 / (cv * P) > 0 ? 256 / (cv * P) : 1;
-        if (C % 8 == 0 && ld % 8 == 0 && cv <= 256 && Bg % ipb == 0 && HW >= P) {
-            DISPATCH_T(dtype, hipLaunchKernelGGL((pool_bwd8_kernel<T>), dim3((B + ipb - 1) / ipb), dim3(256), 2 * C * sizeof(double),
-                                                 (hipStream_t)stream, (const T*)x, scale, shift, slope, mean, rstd, dfeat, B, HW, C, ld,
-                                                 (T*)g, bsums, Bg, P));
-            return sv_check_launch("sv_pool_bwd");
-        }
+    const int Bg = B / sv_ngroups(groups);
+    int P, ipb;
+    if (pool8_shape(Bg, HW, C, ld, P, ipb)) {
+        DISPATCH_T(dtype, hipLaunchKernelGGL((pool_bwd8_kernel<T>), dim3((B + ipb - 1) / ipb), dim3(256), 2 * C * sizeof(double),
+                                             (hipStream_t)stream, (const T*)x, scale, shift, slope, mean, rstd, dfeat, B, HW, C, ld,
+                                             (T*)g, bsums, Bg, P));
+        return sv_check_launch("sv_pool_bwd");
     }
     DISPATCH_T(dtype, hipLaunchKernelGGL((pool_bwd_kernel<T>), dim3((B * C + 255) / 256), dim3(256), 0,
                                          (hipStream_t)stream, (const T*)x, scale, shift, slope, mean, rstd, dfeat,
-                                         B, HW, C, ld, (T*)g, bsums, B / sv_ngroups(groups)));
+                                         B, HW, C, ld, (T*)g, bsums, Bg));
     return sv_check_launch("sv_pool_bwd");
 }
 

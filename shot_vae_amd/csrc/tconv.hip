@@ -144,7 +144,7 @@ __global__ __launch_bounds__(512, 1) void tconvr_kernel(const sv_geom g, const s
     for (int j = 0; j < KL; ++j) *reinterpret_cast<bf16x8*>(wlds + j * 1024) = wtail[j];
     // (BatchNorm finalisation folded into this launch -- sv_igemm_args::fold_*: every block derives the coefficients itself, block 0
     //  of a group stores the four vectors; the scratch lies in the image area, zeroed below)
-    if (!EX && a.fold_stats) sv_bn_fold_block512(a, CIN, reinterpret_cast<double*>(smem), coef, blockIdx.x == 0);
+    if (!EX && a.fold_stats) sv_bn_fold_block<512, true>(a, CIN, reinterpret_cast<double*>(smem), coef, coef + 1, blockIdx.x == 0);
     else if (has_pro && tid < 2 * CIN) coef[tid] = (tid & 1) ? a.pro_shift[tid >> 1] : a.pro_scale[tid >> 1];      // [CIN] pairs {scale, shift}
     if (EX && tid < NOUT) {       // (EX: the area holds the epilogue's per-channel constants instead -- no prologue there)
         const float rs = a.ex_rstd[tid];
@@ -494,14 +494,8 @@ int launch_tconvr(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const int grid = sv_block_slots(g->B, sv_persistent_blocks() / 2 / G);      // (the budget counts two blocks per CU; this kernel is one: 512 registers)
     static bool optin = false;
     if (const int rc = sv_lds_optin(optin, C::LDS, "tconvr", &tconvr_kernel<CIN, NOUT, H, EX>)) return rc;
-    sv_igemm_args b = *a;          // the forward form folds the BatchNorm finalisation of its prologue
-    if (!sv_fold_claim(!EX && b.fold_stats != nullptr)) b.fold_stats = nullptr;
-    a = &b;
-    SV_LAUNCH_GATE(grid, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((tconvr_kernel<CIN, NOUT, H, EX>), dim3(grid, G), dim3(C::NTH), C::LDS, s, *g, sv_expand_groups(*g, *a, 2));
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(tconvr)");
+    const sv_igemm_args b = sv_fold_resolve(*a, !EX && a->fold_stats != nullptr);      // the forward form folds the BatchNorm finalisation of its prologue
+    return sv_igemm_launch(&tconvr_kernel<CIN, NOUT, H, EX>, grid, C::NTH, C::LDS, g, &b, 2, s, "sv_igemm(tconvr)");
 }
 
 // ---- the 32 <- 64 stride-2 3x3 data gradient (wideresnet.py:29-30, the first convolution of block 2: dy 16x16x64 -> dx 32x32x32)
@@ -581,7 +575,7 @@ __global__ __launch_bounds__(512, 1) void tconvx16_kernel(const sv_geom g, const
     }
     // (FWD: the area holds the prologue's [CIN] pairs {scale, shift}; the folded finalisation's scratch lies in the image area,
     //  zeroed below)
-    if (FWD && a.fold_stats) sv_bn_fold_block512(a, CIN, reinterpret_cast<double*>(smem), cst, blockIdx.x == 0);
+    if (FWD && a.fold_stats) sv_bn_fold_block<512, true>(a, CIN, reinterpret_cast<double*>(smem), cst, cst + 1, blockIdx.x == 0);
     else if (has_pro && tid < 2 * CIN) cst[tid] = (tid & 1) ? a.pro_shift[tid >> 1] : a.pro_scale[tid >> 1];
     {
         bf16x8 z;
@@ -806,14 +800,8 @@ int launch_tconvx16(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const int grid = sv_block_slots(g->B, sv_persistent_blocks() / 2 / G);
     static bool optin = false;
     if (const int rc = sv_lds_optin(optin, C::LDS, "tconvx16", &tconvx16_kernel<FWD>)) return rc;
-    sv_igemm_args b = *a;          // the forward form folds the BatchNorm finalisation of its prologue
-    if (!sv_fold_claim(FWD && b.fold_stats != nullptr)) b.fold_stats = nullptr;
-    a = &b;
-    SV_LAUNCH_GATE(grid, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((tconvx16_kernel<FWD>), dim3(grid, G), dim3(C::NTH), C::LDS, s, *g, sv_expand_groups(*g, *a, 2));
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(tconvx16)");
+    const sv_igemm_args b = sv_fold_resolve(*a, FWD && a->fold_stats != nullptr);      // the forward form folds the BatchNorm finalisation of its prologue
+    return sv_igemm_launch(&tconvx16_kernel<FWD>, grid, C::NTH, C::LDS, g, &b, 2, s, "sv_igemm(tconvx16)");
 }
 
 }  // namespace

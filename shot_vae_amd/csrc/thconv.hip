@@ -242,11 +242,7 @@ int launch_thconv(const sv_geom* g, const sv_igemm_args* a, hipStream_t s) {
     const int G = sv_ngroups(a->groups);
     const int nband = g->B * (C::W / 8);
     const int grid = sv_block_slots(nband, sv_persistent_blocks() / 2 / G);      // (the budget counts two blocks per CU; this kernel is one)
-    SV_LAUNCH_GATE(grid, a);
-    sv_prof_begin(s);
-    hipLaunchKernelGGL((thconv_kernel<CIN, NOUT>), dim3(grid, G), dim3(C::NTH), C::LDS, s, *g, sv_expand_groups(*g, *a, 2));
-    sv_prof_end(s);
-    return sv_check_launch("sv_igemm(thconv)");
+    return sv_igemm_launch(&thconv_kernel<CIN, NOUT>, grid, C::NTH, C::LDS, g, a, 2, s, "sv_igemm(thconv)");
 }
 
 }  // namespace
