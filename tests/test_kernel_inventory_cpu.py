@@ -23,11 +23,6 @@ ALLOWED = {
     "sv_bn_running_update_ex": "engine's deferred running-stat update: tests/test_model_gpu.py::test_step_matches_oracle_b64 "
                                "(running_mean / running_var against the oracle)",
     "sv_repack_strided": "sv_repack is this function with dense strides: every sv_repack of tests/test_kernels_gpu.py",
-    "sv_shot_targets": "steploss.shot_losses: tests/test_model_gpu.py::test_fused_loss_node_equals_modular_criteria",
-    "sv_shot_targets2": "inside sv_shot_loss_step2: tests/test_model_gpu.py::test_fused_loss_node_equals_modular_criteria",
-    "sv_shot_compose": "steploss.shot_losses: tests/test_model_gpu.py::test_fused_loss_node_equals_modular_criteria",
-    "sv_shot_scale": "steploss.shot_losses backward: tests/test_model_gpu.py::test_fused_loss_node_equals_modular_criteria",
-    "sv_shot_loss_step2": "steploss.shot_loss_step: tests/test_model_gpu.py::test_fused_loss_node_equals_modular_criteria",
 }
 
 
