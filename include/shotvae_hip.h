@@ -332,6 +332,23 @@ int sv_head_bwd(const float* feat, int B, int C, const float* W, int ldc, int K,
                 const float* dmu, const float* dls, const float* dla, float* dfeat, float* dW,
                 float* dbias, float* dout_ws, void* stream);
 
+/* ---- classifier tail (classifier_model/wideresnet.py:94-102, main_classifier.py:101): one Linear(C, K) that returns the raw
+ * logits, and nn.CrossEntropyLoss() (mean) on int64 labels.  Added under ABI 8: new symbols only, no struct or signature changed.
+ * sv_fc_fwd: logits [B][K] = feat [B][C] . W^T ([K][C]) + bias, fp32.
+ * sv_fc_bwd: dfeat [B][C] = dlogits . W is WRITTEN; dW / dbias accumulate (+=) through the heads' weight-gradient kernel (in
+ *   deterministic mode its 128-sample slices run one after the other).
+ * sv_ce_fwd: row_loss[b] = logsumexp(logits[b]) - logits[b][label[b]] ([B], may be NULL); *loss is WRITTEN = their mean, summed
+ *   by one block in a fixed order (no atomics, no pre-zeroed output, the same bits in every mode).  A label outside [0, K) is
+ *   never used as an index: that row's loss, and so the mean, is NaN.
+ * sv_ce_bwd: dlogits[b] = (softmax(logits[b]) - onehot(label[b])) * gout[0] / B (gout: device scalar); all zeros for a row whose
+ *   label is outside [0, K).
+ * Null pointers and non-positive sizes are refused before any launch.                                                      */
+int sv_fc_fwd(const float* feat, int B, int C, const float* W, const float* bias, int K, float* logits, void* stream);
+int sv_fc_bwd(const float* feat, int B, int C, const float* W, int K, const float* dlogits, float* dfeat, float* dW,
+              float* dbias, void* stream);
+int sv_ce_fwd(const float* logits, const int64_t* label, int B, int K, float* row_loss, float* loss, void* stream);
+int sv_ce_bwd(const float* logits, const int64_t* label, int B, int K, const float* gout, float* dlogits, void* stream);
+
 /* ---- K10/K11 reparameterisation sampler (vae.py:23-86) -------------------------------------------
  * mode 0: gumbel-softmax from u; 1: one-hot(label); 2: lam*onehot(label)+(1-lam)*onehot(label_mix).
  * latent is [B][Lpad] of `dtype` = [z | c | 0-pad]; csoft [B][K] fp32 keeps c for the backward.     */

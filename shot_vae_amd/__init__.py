@@ -8,6 +8,8 @@ from .optim import FlatSGD, FlatAdam              # noqa: F401
 from .train import (train_step, train_step_overlapped, train_step_grouped, GraphedTrainStep, DeviceRng, schedule,   # noqa: F401
                     alpha_schedule, m2_train_step, apply_update, inference_kl)
 from .evaluate import Evaluator, evaluate       # noqa: F401
+from .classifier import (WideResNetClassifier, get_wide_resnet, CrossEntropyLoss, classifier_train_step,      # noqa: F401
+                         GraphedClassifierStep, ClassifierEvaluator, evaluate_classifier)
 from .data import DeviceDataset, ssl_split      # noqa: F401
 from .smooth import (SmoothVAE, svhn_VAE, mnist_VAE, SmoothELBOLoss, smooth_train_step,      # noqa: F401
                      GraphedSmoothStep)

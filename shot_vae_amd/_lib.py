@@ -136,6 +136,10 @@ _PROTOS = {
     "sv_pool_bwd": [I, P, P, P, F, P, P, P, I, I, I, I, P, P, I, P],
     "sv_head_fwd": [P, I, I, P, P, I, I, P, P, P, P],
     "sv_head_bwd": [P, I, I, P, I, I, P, P, P, P, P, P, P, P, P],
+    "sv_fc_fwd": [P, I, I, P, P, I, P, P],
+    "sv_fc_bwd": [P, I, I, P, I, P, P, P, P, P],
+    "sv_ce_fwd": [P, P, I, I, P, P, P],
+    "sv_ce_bwd": [P, P, I, I, P, P, P],
     "sv_sample_fwd": [I, P, P, P, P, P, P, P, F, P, I, F, I, I, I, I, P, P, P],
     "sv_sample_bwd": [I, P, P, P, P, I, F, I, I, I, I, P, P, P, P],
     "sv_elbo_fwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P],

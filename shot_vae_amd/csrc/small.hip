@@ -837,6 +837,126 @@ __global__ __launch_bounds__(64) void head_bwd_weight_kernel(const float* feat, 
     }
 }
 
+// ---------------------------------------------------------------------------------------- classifier tail
+// logits[b][n] = feat[b] . W[n] + bias[n] (classifier_model/wideresnet.py:94-102: raw logits, no log-softmax).  grid =
+// (ceil(B / HS), ceil(K / FC_NB)): a block owns HS samples (their features in LDS) and FC_NB outputs; its four waves take the
+// outputs in turn, one wave per dot product: the weight row is read coalesced, lane-strided over C, and summed across the wave in a
+// fixed order.  (One block per HS samples for all K outputs left a wave 25 dependent dot products at K = 100, each waiting for its
+// own weight loads: 115 us at C = 640 whatever the batch.)
+constexpr int FC_NB = 16;   // outputs per block
+__global__ __launch_bounds__(256) void fc_fwd_kernel(const float* feat, int B, int C, const float* W, const float* bias, int K,
+                                                     float* logits) {
+    extern __shared__ __attribute__((aligned(16))) float hs[];      // [HS][C]
+    const int b0 = blockIdx.x * HS;
+    const int n1 = min(K, (int)(blockIdx.y + 1) * FC_NB);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < HS * C; i += 256) {
+        const int s = i / C;
+        hs[i] = (b0 + s < B) ? feat[(int64_t)(b0 + s) * C + (i - s * C)] : 0.f;
+    }
+    __syncthreads();
+    for (int n = blockIdx.y * FC_NB + wave; n < n1; n += 4) {
+        const float* wr = W + (int64_t)n * C;
+        float acc[HS];
+#pragma unroll
+        for (int s = 0; s < HS; ++s) acc[s] = 0.f;
+#pragma unroll 4
+        for (int c = lane; c < C; c += 64) {
+            const float w = wr[c];
+#pragma unroll
+            for (int s = 0; s < HS; ++s) acc[s] += w * hs[s * C + c];
+        }
+        const float bb = bias[n];
+#pragma unroll
+        for (int s = 0; s < HS; ++s) {
+            const float t = wave_sum(acc[s]);
+            if (lane == 0 && b0 + s < B) logits[(int64_t)(b0 + s) * K + n] = t + bb;
+        }
+    }
+}
+
+// dfeat[b][c] = sum_n dlogits[b][n] * W[n][c] (written).  grid = (ceil(B / HS), ceil(C / 256)): a block holds its HS gradient
+// rows in LDS, a thread owns one channel of the block's 256-channel slice (the weight reads are coalesced over c).
+__global__ __launch_bounds__(256) void fc_bwd_data_kernel(int B, int C, const float* W, int K, const float* dlogits, float* dfeat) {
+    extern __shared__ __attribute__((aligned(16))) float hs[];      // [HS][K]
+    const int b0 = blockIdx.x * HS;
+    const int tid = threadIdx.x;
+    for (int i = tid; i < HS * K; i += 256) {
+        const int s = i / K;
+        hs[i] = (b0 + s < B) ? dlogits[(int64_t)(b0 + s) * K + (i - s * K)] : 0.f;
+    }
+    __syncthreads();
+    const int c = blockIdx.y * 256 + tid;
+    if (c >= C) return;
+    float acc[HS];
+#pragma unroll
+    for (int s = 0; s < HS; ++s) acc[s] = 0.f;
+#pragma unroll 4
+    for (int n = 0; n < K; ++n) {
+        const float w = W[(int64_t)n * C + c];
+#pragma unroll
+        for (int s = 0; s < HS; ++s) acc[s] += w * hs[s * K + n];
+    }
+#pragma unroll
+    for (int s = 0; s < HS; ++s)
+        if (b0 + s < B) dfeat[(int64_t)(b0 + s) * C + c] = acc[s];
+}
+
+// log-sum-exp of one row of logits by one wave, stable (the row maximum is subtracted first); every lane returns it
+__device__ __forceinline__ float ce_row_lse(const float* z, int K, int lane) {
+    float mx = -INFINITY;
+    for (int k = lane; k < K; k += 64) mx = fmaxf(mx, z[k]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    float se = 0.f;
+    for (int k = lane; k < K; k += 64) se += expf(z[k] - mx);
+    return mx + logf(wave_sum(se));
+}
+
+// nn.CrossEntropyLoss() (main_classifier.py:101): row loss = lse(z) - z[label], loss = their mean.  ONE block: wave w takes rows
+// w, w + 16, ... and adds their losses in that order, the sixteen partial sums meet in LDS in wave order -- no atomics, nothing to
+// zero, the same bits in every run.  A label outside [0, K) is never an index: that row's loss is NaN (and so is the mean).
+constexpr int CE_WAVES = 16;
+__global__ __launch_bounds__(64 * CE_WAVES) void ce_fwd_kernel(const float* logits, const int64_t* label, int B, int K,
+                                                               float* row_loss, float* loss) {
+    __shared__ float part[CE_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float acc = 0.f;
+    for (int b = wave; b < B; b += CE_WAVES) {
+        const float* z = logits + (int64_t)b * K;
+        const float lse = ce_row_lse(z, K, lane);
+        const int64_t y = label[b];
+        const float l = (y >= 0 && y < K) ? lse - z[y] : NAN;
+        acc += l;
+        if (row_loss && lane == 0) row_loss[b] = l;
+    }
+    if (lane == 0) part[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int w = 0; w < CE_WAVES; ++w) t += part[w];
+        *loss = t / (float)B;
+    }
+}
+
+// dlogits[b][k] = (softmax(z[b])[k] - [k == label[b]]) * gout / B; one wave per row.  A row whose label is outside [0, K) gets zeros.
+__global__ __launch_bounds__(256) void ce_bwd_kernel(const float* logits, const int64_t* label, int B, int K, const float* gout,
+                                                     float* dlogits) {
+    const int lane = threadIdx.x & 63;
+    const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const float* z = logits + (int64_t)b * K;
+    float* d = dlogits + (int64_t)b * K;
+    const int64_t y = label[b];
+    if (y < 0 || y >= K) {
+        for (int k = lane; k < K; k += 64) d[k] = 0.f;
+        return;
+    }
+    const float lse = ce_row_lse(z, K, lane);
+    const float g = gout[0] / (float)B;
+    for (int k = lane; k < K; k += 64) d[k] = (expf(z[k] - lse) - (k == (int)y ? 1.f : 0.f)) * g;
+}
+
 // ---------------------------------------------------------------------------------------- sampler
 template <typename T>
 __global__ __launch_bounds__(128) void sample_fwd_kernel(const float* mu, const float* ls, const float* la,
@@ -2066,6 +2186,19 @@ int sv_head_fwd(const float* feat, int B, int C, const float* W, const float* bi
     return sv_check_launch("sv_head_fwd");
 }
 
+// the weight / bias gradient launches of head_bwd_weight_kernel for dout [B][NH]: one launch over every 128-sample slice, or, in
+// deterministic mode, the slices one after the other (one adder per address at any time)
+static void launch_head_bwd_weight(const float* feat, const float* dout, int B, int C, int NH, float* dW, float* dbias, hipStream_t stream) {
+    const int tiles = ((NH + 31) / 32) * ((C + 31) / 32);
+    const int slices = (B + HWS - 1) / HWS;
+    if (sv_deterministic()) {
+        for (int sl = 0; sl < slices; ++sl)
+            hipLaunchKernelGGL(head_bwd_weight_kernel, dim3(tiles, 1), dim3(64), 0, stream, feat, dout, B, C, NH, dW, dbias, sl);
+    } else {
+        hipLaunchKernelGGL(head_bwd_weight_kernel, dim3(tiles, slices), dim3(64), 0, stream, feat, dout, B, C, NH, dW, dbias, 0);
+    }
+}
+
 int sv_head_bwd(const float* feat, int B, int C, const float* W, int ldc, int K, const float* la,
                    const float* dmu, const float* dls, const float* dla, float* dfeat, float* dW, float* dbias,
                    float* dout_ws, void* stream) {
@@ -2075,19 +2208,45 @@ int sv_head_bwd(const float* feat, int B, int C, const float* W, int ldc, int K,
     const size_t lds = ((size_t)HS * NH + (size_t)HS * 256) * sizeof(float);       // gradients + the thread groups' partial sums
     hipLaunchKernelGGL(head_bwd_data_kernel, dim3((B + HS - 1) / HS, (C + 255) / 256), dim3(256), lds, (hipStream_t)stream, B, C, W,
                        ldc, K, la, dmu, dls, dla, dfeat, dout_ws);
-    {
-        const int tiles = ((NH + 31) / 32) * ((C + 31) / 32);
-        const int slices = (B + HWS - 1) / HWS;
-        if (sv_deterministic()) {
-            for (int sl = 0; sl < slices; ++sl)
-                hipLaunchKernelGGL(head_bwd_weight_kernel, dim3(tiles, 1), dim3(64), 0, (hipStream_t)stream, feat, dout_ws, B, C,
-                                   NH, dW, dbias, sl);
-        } else {
-            hipLaunchKernelGGL(head_bwd_weight_kernel, dim3(tiles, slices), dim3(64), 0, (hipStream_t)stream, feat, dout_ws, B, C,
-                               NH, dW, dbias, 0);
-        }
-    }
+    launch_head_bwd_weight(feat, dout_ws, B, C, NH, dW, dbias, (hipStream_t)stream);
     return sv_check_launch("sv_head_bwd");
+}
+
+int sv_fc_fwd(const float* feat, int B, int C, const float* W, const float* bias, int K, float* logits, void* stream) {
+    SvProfScope prof_scope(stream);
+    SV_REQUIRE(feat && W && bias && logits && B > 0 && C > 0 && K > 0, SV_E_ARG, "sv_fc_fwd: null pointer or non-positive size (B=%d C=%d K=%d)", B, C, K);
+    const size_t lds = (size_t)HS * C * sizeof(float);
+    SV_REQUIRE(lds <= 64 * 1024, SV_E_SHAPE, "sv_fc_fwd: C=%d too large", C);
+    hipLaunchKernelGGL(fc_fwd_kernel, dim3((B + HS - 1) / HS, (K + FC_NB - 1) / FC_NB), dim3(256), lds, (hipStream_t)stream, feat, B, C, W,
+                       bias, K, logits);
+    return sv_check_launch("sv_fc_fwd");
+}
+
+int sv_fc_bwd(const float* feat, int B, int C, const float* W, int K, const float* dlogits, float* dfeat, float* dW, float* dbias,
+              void* stream) {
+    SvProfScope prof_scope(stream);
+    SV_REQUIRE(feat && W && dlogits && dfeat && dW && dbias && B > 0 && C > 0 && K > 0, SV_E_ARG,
+               "sv_fc_bwd: null pointer or non-positive size (B=%d C=%d K=%d)", B, C, K);
+    const size_t lds = (size_t)HS * K * sizeof(float);
+    SV_REQUIRE(lds <= 64 * 1024, SV_E_SHAPE, "sv_fc_bwd: K=%d too large", K);
+    hipLaunchKernelGGL(fc_bwd_data_kernel, dim3((B + HS - 1) / HS, (C + 255) / 256), dim3(256), lds, (hipStream_t)stream, B, C, W, K,
+                       dlogits, dfeat);
+    launch_head_bwd_weight(feat, dlogits, B, C, K, dW, dbias, (hipStream_t)stream);
+    return sv_check_launch("sv_fc_bwd");
+}
+
+int sv_ce_fwd(const float* logits, const int64_t* label, int B, int K, float* row_loss, float* loss, void* stream) {
+    SvProfScope prof_scope(stream);
+    SV_REQUIRE(logits && label && loss && B > 0 && K > 0, SV_E_ARG, "sv_ce_fwd: null pointer or non-positive size (B=%d K=%d)", B, K);
+    hipLaunchKernelGGL(ce_fwd_kernel, dim3(1), dim3(64 * CE_WAVES), 0, (hipStream_t)stream, logits, label, B, K, row_loss, loss);
+    return sv_check_launch("sv_ce_fwd");
+}
+
+int sv_ce_bwd(const float* logits, const int64_t* label, int B, int K, const float* gout, float* dlogits, void* stream) {
+    SvProfScope prof_scope(stream);
+    SV_REQUIRE(logits && label && gout && dlogits && B > 0 && K > 0, SV_E_ARG, "sv_ce_bwd: null pointer or non-positive size (B=%d K=%d)", B, K);
+    hipLaunchKernelGGL(ce_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, label, B, K, gout, dlogits);
+    return sv_check_launch("sv_ce_bwd");
 }
 
 int sv_sample_fwd(int dtype, const float* mu, const float* ls, const float* la, const float* eps, const float* u,

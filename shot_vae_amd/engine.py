@@ -18,6 +18,7 @@ import ctypes as C
 import os
 import math
 import re
+import types
 
 import torch
 
@@ -132,8 +133,17 @@ class BNSpec:
 class Plan:
     """Architecture + memory layout (device independent)."""
 
-    def __init__(self, encoder_name, in_ch=3, img=32, ldc=128, K=10, drop_rate=0.0):
+    def __init__(self, encoder_name, in_ch=3, img=32, ldc=128, K=10, drop_rate=0.0, head="vae"):
+        """head = "vae": the encoder, the three inference heads and the decoder of shot_vae_model/vae.py; "classifier": the same
+        encoder under the key names of classifier_model/wideresnet.py:76-102 and ONE Linear(C, K) behind the pool -- no three-head
+        matrix, no decoder (ldc is unused)."""
+        if head not in ("vae", "classifier"):
+            raise ValueError("Plan: head is 'vae' or 'classifier', got %r" % (head,))
         fam = encoder_family(encoder_name)
+        if head == "classifier" and "wideresnet" not in encoder_name:
+            raise NotImplementedError("the classifier baseline is built for the wideresnet-D-W encoders (main_classifier.py builds "
+                                      "nothing else); got %s" % encoder_name)
+        self.head = head
         if img != 32 or in_ch > CPAD:
             raise NotImplementedError("the MI355X path covers 32x32 inputs with <= 16 channels "
                                       "(BASELINE.json configs); got img=%s ch=%s" % (img, in_ch))
@@ -173,7 +183,7 @@ class Plan:
             self.bns.append(b)
             return b
 
-        enc = "feature_extractor.encoder."
+        enc = "feature_extractor.encoder." if head == "vae" else "encoder."
         self.stem = add_conv(ConvSpec(enc + "pre_process.conv0", "conv", 3, 1, 1, CPAD, self.stem_n, img,
                                       cin_real=in_ch))
         self.stem_bias_off = add_vec(enc + "pre_process.conv0.bias", self.stem_n)
@@ -195,7 +205,23 @@ class Plan:
                 self.units.append(unit)
             cin = w
         self.hfeat = h
-        self.bn_t = add_bn(enc + "transition.norm", self.cfeat, fam["slope"])
+        self.bn_t = add_bn((enc + "transition.norm") if head == "vae" else "global_avg.norm", self.cfeat, fam["slope"])
+        self.dec_convs, self.dec_bns = [], []
+        if head == "classifier":
+            # classifier_model/wideresnet.py:79-102: the modules the reference wraps in nn.DataParallel, and the one [K][C] matrix
+            self.dp_wrapped = tuple([enc + "pre_process"] + [enc + (fam["block"] % (s + 1)).split(".")[0] for s in range(len(self.widths))] +
+                                    ["global_avg", "classification"])
+            self.fc_w_off = alloc(K * self.cfeat)
+            self.fc_b_off = alloc(K)
+            self.params.append(("classification.fc.weight", (self.fc_w_off, (K, self.cfeat))))
+            self.params.append(("classification.fc.bias", (self.fc_b_off, K)))
+            self.n_param = self.dec_off = off[0]
+        else:
+            self._add_vae_tail(enc, fam, in_ch, ldc, K, alloc, add_conv, add_bn, off)
+        self._layout_buffers()
+
+    def _add_vae_tail(self, enc, fam, in_ch, ldc, K, alloc, add_conv, add_bn, off):
+        """the three heads' shared matrix and the decoder (vae.py:108-132, decoder.py:12-58)"""
         # state_dict prefixes of the sub-modules the reference wraps in nn.DataParallel (data_parallel=True key layout)
         self.dp_wrapped = tuple([enc + "pre_process"] + [enc + (fam["block"] % (s + 1)).split(".")[0] for s in range(len(self.widths))] +
                                 [enc + "transition", "continuous_inference.mean", "continuous_inference.log_sigma",
@@ -212,7 +238,6 @@ class Plan:
         # decoder (decoder.py:12-58): ConvT(latent,1024,k=img/32) then 5x ConvT(4,2,1)
         dec = "feature_reconstructor.decoder."
         chans = [1024, 512, 256, 128, 64]
-        self.dec_convs, self.dec_bns = [], []
         self.dec_convs.append(add_conv(ConvSpec(dec + "0", "convT", 1, 1, 0, self.Lpad, chans[0], 1,
                                                 cin_real=ldc + K)))
         hh = 1
@@ -224,6 +249,8 @@ class Plan:
             hh *= 2
         self.n_param = off[0]
         self.dec_off = self.dec_convs[0].master_off     # the decoder's parameters are the tail [dec_off, n_param) of the flat buffer
+
+    def _layout_buffers(self):
         # BN running statistics and per-forward scratch
         o = 0
         for b in self.bns:
@@ -391,6 +418,27 @@ class Engine:
                     self.param[off: off + n] = ((torch.rand(n, generator=g) * 2 - 1) / math.sqrt(p.cfeat)).to(self.param.device)
                 elif key.endswith(".weight"):
                     self.param[off: off + n] = 1.0
+        self.mark_dirty()
+
+    def init_classifier(self, seed=None):
+        """The explicit initialisation of classifier_model/wideresnet.py:104-118 (the same distributions, an RNG stream of its
+        own): conv weights kaiming_uniform_ with a = 0, U(+-sqrt(6 / fan_in)); fc.weight xavier_uniform_, U(+-sqrt(6 / (C + K)));
+        every conv and fc bias 0; BatchNorm weight 1, bias 0."""
+        g = torch.Generator()
+        g.manual_seed(seed if seed is not None else int(torch.randint(0, 2 ** 31 - 1, (1,))))
+        p = self.plan
+        self.param.zero_()
+        for key, kind, payload in p.state_items():
+            if kind == "conv":
+                v = payload.torch_view(self.param)
+                bound = math.sqrt(6.0 / (v.shape[1] * v.shape[2] * v.shape[3]))
+                v.copy_((torch.rand(v.shape, generator=g) * 2 - 1) * bound)
+            elif kind == "mat":
+                off, (r, c) = payload
+                self.param[off: off + r * c] = ((torch.rand(r * c, generator=g) * 2 - 1) * math.sqrt(6.0 / (r + c))).to(self.param.device)
+            elif kind == "vec" and key.endswith(".weight"):          # (BatchNorm weight; the biases stay 0)
+                off, n = payload
+                self.param[off: off + n] = 1.0
         self.mark_dirty()
 
     def mark_dirty(self):
@@ -732,50 +780,14 @@ class Engine:
             lay = self._bn_layouts[G] = (off, o)
         return lay
 
-    def forward(self, image, groups, eps, u, temperature, training, keep, rec_groups=None, update_order=None, x16=None,
-                keys=None):
-        """One BATCHED forward of G = len(groups) independent instances of the network that share the weights (the
-        forwards (1)-(4) of a SHOT-VAE step, main_shot_vae.py:288,311,329,356, or a single one): every launch carries
-        the G groups (sv_igemm_args::groups), each with its OWN BatchNorm batch statistics -- the reference's
-        semantics of separate model(...) calls -- so the step costs a quarter of the launches at four times the rows.
-
-        image   NCHW fp32 on device, [G * B] images: the groups back to back, B images each
-        groups  list of (mode, label, label_mix, lam): the sampler mode of each group (vae.py:38-52): 0 Gumbel-softmax,
-                1 one-hot(label), 2 lam * onehot(label) + (1 - lam) * onehot(label_mix)
-        eps, u  [G * B, ldc] Gaussian noise, [G * B, K] uniform noise (rows of groups with mode != 0 are ignored) or None
-        rec_groups  Gd <= G: only the first Gd groups' reconstructions are produced (and their decoder differentiated).  The
-                reconstructions of the mixed forwards (2) and (4) enter no loss term (main_shot_vae.py:311,356: `*_`), so the
-                step puts (1) and (3) first and skips the last ConvTranspose of the other two and their whole decoder
-                backward -- the decoder up to its last BatchNorm still runs for every group: its running statistics are
-                updated by every train-mode forward.  rec is then [Gd * B, ...].
-        update_order  order[k] = the group of the reference's k-th forward (running-statistic updates; default group order)
-        x16     optional: the NHWC16 image tensor (sv_nchw_to_nhwc of `image`) when the caller has already made it -- the
-                grouped step converts on its input-side stream, beside the previous step's backward
-        keys    dropout (drop_rate > 0, training only): int64 [G] device tensor, the mask key of each group (sv_dropout_args);
-                ignored in eval mode, where dropout is the identity
-        Returns (rec NCHW fp32, mu, ls, la, ctx-or-None), all [G * B, ...]."""
-        self._require_gpu(image)
+    def _fwd_scratch(self, B, G, training, dev):
+        """The scratch of one forward of G groups of B images and the BatchNorm helpers over it, shared by the encoder
+        (_encoder_forward) and whatever tail follows it: .finalize(b, stat_name, count, fold) -> (scale, shift, slope[, fold]) of
+        BatchNorm b, .sptr(name) -> the statistics accumulator of tensor `name` for the launch that produces it, and the buffers
+        themselves (.stats, .bnbuf, .bn_off; deterministic mode: .det, .det_stats)."""
         p = self.plan
-        G = len(groups)
-        drop = training and self.drop_rate > 0
-        if drop:
-            if keys is None or not torch.is_tensor(keys) or keys.dtype != torch.int64 or keys.numel() != G or not keys.is_cuda:
-                raise ValueError("a training forward with drop_rate > 0 needs the dropout keys: an int64 device tensor of %d "
-                                 "(one per group)" % G)
-            keys = keys.contiguous()
-        Bt = image.shape[0]
-        assert Bt % G == 0, "the groups of a batched forward have equal batch sizes"
-        B = Bt // G
-        Gd = G if rec_groups is None else int(rec_groups)
-        assert 0 <= Gd <= G
-        dev = image.device
-        T = self.tdtype
         st = self._stream()
-        self.ensure_packs()
-        image = image.contiguous().float()
         pbase, bbase = self.param.data_ptr(), self.bufs.data_ptr()
-        pk, es = self.packs.data_ptr(), self.packs.element_size()
-
         # per-forward scratch: BN statistics [G][R][2C] (zeroed), BN affine/mean/rstd [G][C]
         n_stat = 0
         stat_off, stat_rep, stat_c = {}, {}, {}
@@ -793,7 +805,7 @@ class Engine:
             hs //= un["stride"]
             stat_slot("c1_%d" % i, un["cout"], B * hs * hs)
             stat_slot("t%d" % (i + 1), un["cout"], B * hs * hs)
-        for i in range(5):
+        for i in range(len(p.dec_bns)):
             stat_slot("h%d" % i, p.dec_convs[i].N, B * p.dec_convs[i].Hout ** 2)
         stats = torch.zeros(n_stat, dtype=torch.float64, device=dev)       # sv_acc_t: the accumulators are doubles (ABI 6)
         sbase = stats.data_ptr()
@@ -845,11 +857,23 @@ class Engine:
                     return t.data_ptr()
                 return alloc
             return (sbase + 8 * stat_off[name], stat_rep[name])
+        return types.SimpleNamespace(finalize=finalize, sptr=sptr, stats=stats, sbase=sbase, stat_off=stat_off, stat_rep=stat_rep,
+                                     bnbuf=bnbuf, bn_off=bn_off, det=det, det_stats=det_stats)
 
-        f = FwdCtx()
-        f.B, f.G, f.groups, f.temperature, f.training = B, G, groups, temperature, training
-        f.Gd = Gd
-        f.bnbuf, f.bn_off = bnbuf, bn_off
+    def _encoder_forward(self, fs, f, image, x16, keys, drop):
+        """Stem, residual units, final BatchNorm + activation + global average pool (wideresnet.py:76-99 / preactresnet.py:94-117 and
+        the pool of vae.py:143 / classifier_model/wideresnet.py:122-123) of the forward whose scratch is `fs`; fills f.x16, f.t,
+        f.c1, f.pro.  Returns (feat [G * B, C] fp32, prot = the final BatchNorm's (scale, shift, slope))."""
+        p = self.plan
+        B, G = f.B, f.G
+        Bt = B * G
+        dev = image.device
+        T = self.tdtype
+        st = self._stream()
+        pbase = self.param.data_ptr()
+        pk, es = self.packs.data_ptr(), self.packs.element_size()
+        finalize, sptr, det, det_stats = fs.finalize, fs.sptr, fs.det, fs.det_stats
+        sbase, stat_off, stat_rep = fs.sbase, fs.stat_off, fs.stat_rep
         # stem (wideresnet.py:13-14, preactresnet.py:8-10): NCHW fp32 -> NHWC16, conv3x3 + bias, stats of t0
         if x16 is None:
             x16 = self.to_nhwc16(image)
@@ -899,6 +923,73 @@ class Engine:
         feat = torch.empty(Bt, p.cfeat, dtype=torch.float32, device=dev)
         L.call("sv_pool_fwd", self.code, _vp(f.t[-1].data_ptr()), _vp(prot[0]), _vp(prot[1]), prot[2], Bt, h * h,
                p.cfeat, p.cfeat, _vp(feat.data_ptr()), G, st)
+        return feat, prot
+
+    def _finish_forward(self, fs, f, training, update_order):
+        """the running-statistic update of a training forward: deferred into its slot (apply_pending), applied at once without one"""
+        if training:
+            # running stats + counter applied by apply_pending(), in slot order (= the reference's forward order)
+            slot = self.defer_slot if self.defer_slot is not None else len(self._pending)
+            self._pending[slot] = (fs.bnbuf, f.B, f.G, update_order)
+            if self.defer_slot is None:
+                self.apply_pending()
+
+    def _check_keys(self, keys, G, drop):
+        """the dropout keys of a forward of G groups as the kernels take them (None without dropout)"""
+        if not drop:
+            return None
+        if keys is None or not torch.is_tensor(keys) or keys.dtype != torch.int64 or keys.numel() != G or not keys.is_cuda:
+            raise ValueError("a training forward with drop_rate > 0 needs the dropout keys: an int64 device tensor of %d "
+                             "(one per group)" % G)
+        return keys.contiguous()
+
+    def forward(self, image, groups, eps, u, temperature, training, keep, rec_groups=None, update_order=None, x16=None,
+                keys=None):
+        """One BATCHED forward of G = len(groups) independent instances of the network that share the weights (the
+        forwards (1)-(4) of a SHOT-VAE step, main_shot_vae.py:288,311,329,356, or a single one): every launch carries
+        the G groups (sv_igemm_args::groups), each with its OWN BatchNorm batch statistics -- the reference's
+        semantics of separate model(...) calls -- so the step costs a quarter of the launches at four times the rows.
+
+        image   NCHW fp32 on device, [G * B] images: the groups back to back, B images each
+        groups  list of (mode, label, label_mix, lam): the sampler mode of each group (vae.py:38-52): 0 Gumbel-softmax,
+                1 one-hot(label), 2 lam * onehot(label) + (1 - lam) * onehot(label_mix)
+        eps, u  [G * B, ldc] Gaussian noise, [G * B, K] uniform noise (rows of groups with mode != 0 are ignored) or None
+        rec_groups  Gd <= G: only the first Gd groups' reconstructions are produced (and their decoder differentiated).  The
+                reconstructions of the mixed forwards (2) and (4) enter no loss term (main_shot_vae.py:311,356: `*_`), so the
+                step puts (1) and (3) first and skips the last ConvTranspose of the other two and their whole decoder
+                backward -- the decoder up to its last BatchNorm still runs for every group: its running statistics are
+                updated by every train-mode forward.  rec is then [Gd * B, ...].
+        update_order  order[k] = the group of the reference's k-th forward (running-statistic updates; default group order)
+        x16     optional: the NHWC16 image tensor (sv_nchw_to_nhwc of `image`) when the caller has already made it -- the
+                grouped step converts on its input-side stream, beside the previous step's backward
+        keys    dropout (drop_rate > 0, training only): int64 [G] device tensor, the mask key of each group (sv_dropout_args);
+                ignored in eval mode, where dropout is the identity
+        Returns (rec NCHW fp32, mu, ls, la, ctx-or-None), all [G * B, ...]."""
+        self._require_gpu(image)
+        p = self.plan
+        G = len(groups)
+        drop = training and self.drop_rate > 0
+        keys = self._check_keys(keys, G, drop)
+        Bt = image.shape[0]
+        assert Bt % G == 0, "the groups of a batched forward have equal batch sizes"
+        B = Bt // G
+        Gd = G if rec_groups is None else int(rec_groups)
+        assert 0 <= Gd <= G
+        dev = image.device
+        T = self.tdtype
+        st = self._stream()
+        self.ensure_packs()
+        image = image.contiguous().float()
+        pbase = self.param.data_ptr()
+        pk, es = self.packs.data_ptr(), self.packs.element_size()
+        fs = self._fwd_scratch(B, G, training, dev)
+        finalize, sptr, stats, bnbuf = fs.finalize, fs.sptr, fs.stats, fs.bnbuf
+
+        f = FwdCtx()
+        f.B, f.G, f.groups, f.temperature, f.training = B, G, groups, temperature, training
+        f.Gd = Gd
+        f.bnbuf, f.bn_off = fs.bnbuf, fs.bn_off
+        feat, prot = self._encoder_forward(fs, f, image, x16, keys, drop)
         mu = torch.empty(Bt, p.ldc, dtype=torch.float32, device=dev)
         ls = torch.empty(Bt, p.ldc, dtype=torch.float32, device=dev)
         la = torch.empty(Bt, p.K, dtype=torch.float32, device=dev)
@@ -954,14 +1045,7 @@ class Engine:
             rec = torch.empty(Gd * B, p.in_ch, p.img, p.img, dtype=torch.float32, device=dev)
             L.call("sv_nhwc_to_nchw", self.code, _vp(f.h[5].data_ptr()), Gd * B, p.in_ch, p.img, p.img, p.dec_convs[5].N,
                    _vp(rec.data_ptr()), st)
-        if training:
-            if defer:      # running stats + counter applied by apply_pending(), in slot order (= the reference's forward order)
-                slot = self.defer_slot if self.defer_slot is not None else len(self._pending)
-                self._pending[slot] = (bnbuf, B, G, update_order)
-                if self.defer_slot is None:
-                    self.apply_pending()
-            else:
-                self.nbt += 1
+        self._finish_forward(fs, f, training, update_order)
         if not keep:
             return rec, mu, ls, la, None
         f.drop_keys = keys if drop else None
@@ -969,6 +1053,48 @@ class Engine:
         f.eps, f.csoft, f.latent = eps, csoft, latent
         f.keep = (groups, u, stats)
         return rec, mu, ls, la, f
+
+    def forward_classifier(self, image, training, keep, keys=None):
+        """The classifier network (Plan(head="classifier"); classifier_model/wideresnet.py:120-125): the shared encoder, then
+        sv_fc_fwd.  One group.  image NCHW fp32 on device; keys: the dropout key (int64 [1] on the device) of a training forward
+        with drop_rate > 0.  Eval mode normalises with the running statistics.  Returns (logits [B, K] fp32, ctx-or-None)."""
+        self._require_gpu(image)
+        p = self.plan
+        drop = training and self.drop_rate > 0
+        keys = self._check_keys(keys, 1, drop)
+        B = image.shape[0]
+        dev = image.device
+        self.ensure_packs()
+        image = image.contiguous().float()
+        fs = self._fwd_scratch(B, 1, training, dev)
+        f = FwdCtx()
+        f.B, f.G, f.training = B, 1, training
+        f.bnbuf, f.bn_off = fs.bnbuf, fs.bn_off
+        feat, prot = self._encoder_forward(fs, f, image, None, keys, drop)
+        logits = torch.empty(B, p.K, dtype=torch.float32, device=dev)
+        L.call("sv_fc_fwd", _vp(feat.data_ptr()), B, p.cfeat, _vp(self.param.data_ptr() + 4 * p.fc_w_off),
+               _vp(self.param.data_ptr() + 4 * p.fc_b_off), p.K, _vp(logits.data_ptr()), self._stream())
+        self._finish_forward(fs, f, training, None)
+        if not keep:
+            return logits, None
+        f.drop_keys = keys if drop else None
+        f.prot, f.feat = prot, feat
+        f.keep = (fs.stats,)
+        return logits, f
+
+    def backward_classifier(self, f, d_logits):
+        """Gradients of forward_classifier's parameters accumulate (+=) into self.grad: sv_fc_bwd, then the shared encoder backward."""
+        self._guarded(self._backward_classifier, f, d_logits)
+
+    def _backward_classifier(self, f, d_logits):
+        p = self.plan
+        pbase, gbase = self.param.data_ptr(), self.grad.data_ptr()
+        bx = self._bwd_scratch(f)
+        d_logits = d_logits.contiguous().float()
+        dfeat = torch.empty(f.B, p.cfeat, dtype=torch.float32, device=d_logits.device)
+        L.call("sv_fc_bwd", _vp(f.feat.data_ptr()), f.B, p.cfeat, _vp(pbase + 4 * p.fc_w_off), p.K, _vp(d_logits.data_ptr()),
+               _vp(dfeat.data_ptr()), _vp(gbase + 4 * p.fc_w_off), _vp(gbase + 4 * p.fc_b_off), self._stream())
+        self._encoder_backward(bx, f, dfeat)
 
     def to_nhwc16(self, image):
         """NCHW fp32 images -> the stem's NHWC tensor with 16 (zero-padded) channels in the compute dtype, on the current stream"""
@@ -1032,8 +1158,11 @@ class Engine:
     def backward(self, f, d_rec, d_mu, d_ls, d_la, own_grads=False):
         """Gradients accumulate (+=) into self.grad; nothing is returned (inputs need no grad).  Batched like the
         forward it belongs to: every launch carries the G groups, the weight gradients sum over them."""
+        self._guarded(self._backward, f, d_rec, d_mu, d_ls, d_la, own_grads)
+
+    def _guarded(self, backward_fn, *args):
         try:
-            self._backward(f, d_rec, d_mu, d_ls, d_la, own_grads)
+            backward_fn(*args)
         except BaseException:
             # the operands kept alive for the side stream must not survive a failed backward into the next step
             if torch.cuda.is_available():
@@ -1042,14 +1171,15 @@ class Engine:
             self._pending_wgrads = []
             raise
 
-    def _backward(self, f, d_rec, d_mu, d_ls, d_la, own_grads=False):
+    def _bwd_scratch(self, f):
+        """The scratch of the backward of forward `f` and the BatchNorm-backward helpers over it, shared by the encoder
+        (_encoder_backward) and the tail in front of it: .bs_off / .bs_rep (per BatchNorm: its (sum g, sum g * xhat) accumulator and
+        replica count), .bnp(b), .ex_of(b, raw), .bn_apply(...), .bn_fold(b, count), .bn_affine(b, count)."""
         p = self.plan
-        B, G, T = f.B, f.G, self.tdtype
-        Bt = B * G
-        dev = f.mu.device
+        B, G = f.B, f.G
+        dev = f.feat.device
         st = self._stream()
         pbase, gbase = self.param.data_ptr(), self.grad.data_ptr()
-        pk, es = self.packs.data_ptr(), self.packs.element_size()
         nb = f.bnbuf.data_ptr()
         # one zeroed scratch for every (sum g, sum g*xhat) pair of this backward: [G][R][2C] per BatchNorm
         bs_rep, bs_rel, tot = {}, {}, 0
@@ -1129,6 +1259,20 @@ class Engine:
             L.call("sv_bn_bwd_affine", _vp(bs_off[b.index]), bs_rep[b.index], b.C, float(count), _vp(pbase + 4 * b.gamma_off), _vp(mn),
                    _vp(rs), _vp(gbase + 4 * b.gamma_off), _vp(gbase + 4 * b.beta_off), _vp(q), _vp(q + 4 * a_), _vp(q + 8 * a_), G, st)
             return coef, q, q + 4 * a_, q + 8 * a_
+        return types.SimpleNamespace(bsums=bsums, bs_off=bs_off, bs_rep=bs_rep, det=det, det_keep=det_keep, bnp=bnp, ex_of=ex_of,
+                                     bn_apply=bn_apply, bn_fold=bn_fold, bn_affine=bn_affine)
+
+    def _backward(self, f, d_rec, d_mu, d_ls, d_la, own_grads=False):
+        p = self.plan
+        B, G, T = f.B, f.G, self.tdtype
+        Bt = B * G
+        dev = f.feat.device
+        st = self._stream()
+        pbase, gbase = self.param.data_ptr(), self.grad.data_ptr()
+        pk, es = self.packs.data_ptr(), self.packs.element_size()
+        nb = f.bnbuf.data_ptr()
+        bx = self._bwd_scratch(f)
+        ex_of, bn_apply = bx.ex_of, bx.bn_apply
 
         # ---- decoder: only the first Gd groups carry a reconstruction gradient (forward(..., rec_groups)); none at all when
         #      the caller's loss does not use the reconstruction (d_rec is None: the mixed forwards of the sequential step) --
@@ -1191,6 +1335,20 @@ class Engine:
                _vp(f.la.data_ptr()), _vp(dmu.data_ptr()), _vp(dls.data_ptr()), _vp(dla.data_ptr()),
                _vp(dfeat.data_ptr()), _vp(gbase + 4 * p.head_w_off), _vp(gbase + 4 * p.head_b_off),
                _vp(ws.data_ptr()), st)
+        self._encoder_backward(bx, f, dfeat)
+
+    def _encoder_backward(self, bx, f, dfeat):
+        """From the gradient of the pooled features (dfeat [G * B, C] fp32) down to the stem: sv_pool_bwd, the final BatchNorm, the
+        residual units last to first, the stem's weight and bias gradients, and the join of the weight-gradient side stream."""
+        p = self.plan
+        B, G = f.B, f.G
+        Bt = B * G
+        dev = dfeat.device
+        st = self._stream()
+        pbase, gbase = self.param.data_ptr(), self.grad.data_ptr()
+        pk, es = self.packs.data_ptr(), self.packs.element_size()
+        det, bs_off, bs_rep = bx.det, bx.bs_off, bx.bs_rep
+        bnp, ex_of, bn_apply, bn_fold, bn_affine = bx.bnp, bx.ex_of, bx.bn_apply, bx.bn_fold, bx.bn_affine
         tl = f.t[-1]
         hw = tl.shape[1] * tl.shape[2]
         g = torch.empty_like(tl)

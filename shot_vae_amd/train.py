@@ -538,7 +538,36 @@ def m2_train_step(model, elbo_criterion, cls_criterion, optimizer, image_l, labe
     return {k: loc[k].detach() for k in keys}
 
 
-class GraphedTrainStep:
+class GraphedStep:
+    """What the captured steps share: a stream of their own, `warmup` eager steps on it, the capture of _body() (forward, loss,
+    backward -- the subclass's) into a hipGraph, and the eager update behind every replay (gradient exchange + optimizer step:
+    the collective stays an ordinary RCCL call and lr can change without re-capturing).  A subclass sets model / opt /
+    distributed, then calls _warm_up() and _capture()."""
+
+    def _warm_up(self, warmup):
+        self.stream = torch.cuda.Stream()
+        cur = torch.cuda.current_stream()
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            for _ in range(warmup):                 # also creates every per-stream cache the capture relies on
+                self._body()
+                self._update()
+        cur.wait_stream(self.stream)
+        torch.cuda.synchronize()
+
+    def _capture(self):
+        self.model._engine.mark_dirty()             # the captured sequence must start with the weight re-packing
+        self.graph = torch.cuda.CUDAGraph()
+        # thread_local: other threads (RCCL's watchdog polling its events at N > 1, the autograd worker's allocator
+        # calls) must not abort the capture
+        with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
+            self.losses = self._body()
+
+    def _update(self):
+        apply_update(self.model, self.opt, self.distributed)
+
+
+class GraphedTrainStep(GraphedStep):
     """(Do not capture while an RCCL (`nccl`) process group has work in flight: its watchdog thread polls events, which is an
     error during another thread's stream capture on this stack -- bench.py issues eagerly in that case.)
     The two-stream step captured once into a hipGraph and replayed: ~1100 kernel launches per step stop costing
@@ -564,23 +593,10 @@ class GraphedTrainStep:
         self.rng = DeviceRng(image_l.device, epsilon, seed=seed)
         self.replays = 0
         self.args = (elbo_criterion, cls_criterion, sch, epsilon)
-        self.stream = torch.cuda.Stream()
-        cur = torch.cuda.current_stream()
-        self.stream.wait_stream(cur)
-        with torch.cuda.stream(self.stream):
-            for _ in range(warmup):                 # also creates every per-stream cache the capture relies on
-                self._body()
-                self._update()
-        cur.wait_stream(self.stream)
-        torch.cuda.synchronize()
+        self._warm_up(warmup)
         self.rng.refill()                           # the warm-up steps consumed entries 0 .. warmup-1: fresh tables,
         self.rng.counter.zero_()                    # and replay k reads entry (k - 1) mod n
-        model._engine.mark_dirty()                  # the captured sequence must start with the weight re-packing
-        self.graph = torch.cuda.CUDAGraph()
-        # thread_local: other threads (RCCL's watchdog polling its events at N > 1, the autograd worker's allocator
-        # calls) must not abort the capture
-        with torch.cuda.graph(self.graph, stream=self.stream, capture_error_mode="thread_local"):
-            self.losses = self._body()
+        self._capture()
 
     def _body(self):
         e, c, sch, eps = self.args
@@ -597,9 +613,6 @@ class GraphedTrainStep:
                                          device_rng=self.rng, optimal_match=self.om, label_u=self.lu)
         finally:
             eng.wgrad_side_stream = keep
-
-    def _update(self):
-        apply_update(self.model, self.opt, self.distributed)
 
     def __call__(self, image_l=None, label_l=None, image_u=None, label_u=None):
         if image_l is not None:

@@ -71,33 +71,28 @@ class _VAEFunction(torch.autograd.Function):
         return (None,) * 9
 
 
-class VariationalAutoEncoder(nn.Module):
-    def __init__(self, encoder_name, num_input_channels=1, drop_rate=0, img_size=(160, 160), data_parallel=True,
-                 continuous_latent_dim=100, disc_latent_dim=10, sample_temperature=0.67, small_input=False,
-                 compute_dtype="bf16", rng="host"):
-        super(VariationalAutoEncoder, self).__init__()
-        # wideresnet-D-W, preactresnet18 / 34; densenet and the bottleneck PreActResNets exist in the reference (vae.py:93-104) but
-        # are not built: NotImplementedError, the reference's fall-through error type (vae.py:106); an unknown preactresnet* name
-        # is the reference's KeyError (preactresnet.py:131)
-        encoder_family(encoder_name)
-        drop_rate = float(drop_rate)
-        if math.isnan(drop_rate) or drop_rate < 0 or drop_rate > 1:
-            raise ValueError("dropout probability has to be between 0 and 1, but got {}".format(drop_rate))
-        if drop_rate == 1:
-            raise NotImplementedError("drop_rate == 1 is not supported: the whole tensor into norm2 would be zero, and its "
-                                      "BatchNorm has no batch statistics to normalise with")
-        if not small_input:
-            raise NotImplementedError("small_input=False (7x7 stem + max-pool) is not implemented; the "
-                                      "CIFAR/SVHN configs of main_shot_vae.py use small_input=True")
-        if tuple(img_size) != (32, 32):
-            raise NotImplementedError("only 32x32 inputs are implemented")
-        plan = Plan(encoder_name, in_ch=num_input_channels, img=img_size[0], ldc=continuous_latent_dim,
-                    K=int(disc_latent_dim), drop_rate=drop_rate)
+def check_drop_rate(drop_rate):
+    """nn.Dropout's range check, and the one rate the kernels do not take"""
+    drop_rate = float(drop_rate)
+    if math.isnan(drop_rate) or drop_rate < 0 or drop_rate > 1:
+        raise ValueError("dropout probability has to be between 0 and 1, but got {}".format(drop_rate))
+    if drop_rate == 1:
+        raise NotImplementedError("drop_rate == 1 is not supported: the whole tensor into norm2 would be zero, and its "
+                                  "BatchNorm has no batch statistics to normalise with")
+    return drop_rate
+
+
+class FlatModule(nn.Module):
+    """A network whose parameters, gradients and BatchNorm buffers live in an Engine's flat buffers: the module tree only names
+    views of them, under the reference's state_dict keys (either data_parallel layout).  Shared by VariationalAutoEncoder and
+    WideResNetClassifier (classifier.py)."""
+
+    TOP_MODULES = ()          # the reference's top-level sub-modules, in its registration order
+
+    def _init_flat(self, plan, compute_dtype, data_parallel, rng, drop_rate):
         self._plan = plan
         self._engine = Engine(plan, compute_dtype)
-        self._temperature = sample_temperature
         self._data_parallel = data_parallel
-        self._disc_latent_dim = disc_latent_dim
         self.rng = rng
         self.drop_rate = drop_rate
         # debugging aid: the int64 [G] dropout-key tensor of every training forward with drop_rate > 0, in call order (the
@@ -105,9 +100,6 @@ class VariationalAutoEncoder(nn.Module):
         # forward's masks (sv_dropout_mask).
         self.last_dropout_keys = []
         self._views = []          # (parameter, flat offset/spec) for re-pointing after device moves
-        self._engine.init_default()
-        self._build_tree()
-        self.feature_extractor.num_feature_channel = plan.cfeat
         self._anchor = None
         # in-place updates by a torch optimizer bump the parameters' version counters: that is how the
         # engine learns that its packed weight shadows are stale
@@ -133,8 +125,7 @@ class VariationalAutoEncoder(nn.Module):
 
     def _build_tree(self):
         eng, plan = self._engine, self._plan
-        for name in ("feature_extractor", "global_avg", "continuous_inference", "disc_latent_inference", "sample",
-                     "feature_reconstructor"):
+        for name in self.TOP_MODULES:
             self.add_module(name, _Node())
         for key, kind, payload in plan.state_items():
             k = _dp_key(key, plan.dp_wrapped) if self._data_parallel else key
@@ -200,11 +191,11 @@ class VariationalAutoEncoder(nn.Module):
             plain = k.replace(".module.", ".")
             alt = _dp_key(plain, self._plan.dp_wrapped) if self._data_parallel else plain
             fixed[alt if alt in own else k] = v
-        out = super(VariationalAutoEncoder, self).load_state_dict(fixed, strict)
+        out = super(FlatModule, self).load_state_dict(fixed, strict)
         self._engine.mark_dirty()
         return out
 
-    # ------------------------------------------------------------------ reference API
+    # ------------------------------------------------------------------ flat buffers, dropout keys
     def flat_parameters(self):
         """(param, grad) flat fp32 buffers: what FlatSGD updates and dp.all_reduce reduces."""
         return self._engine.param, self._engine.grad
@@ -223,6 +214,34 @@ class VariationalAutoEncoder(nn.Module):
         self.last_dropout_keys.append(keys)
         del self.last_dropout_keys[:-16]
 
+
+class VariationalAutoEncoder(FlatModule):
+    TOP_MODULES = ("feature_extractor", "global_avg", "continuous_inference", "disc_latent_inference", "sample", "feature_reconstructor")
+
+    def __init__(self, encoder_name, num_input_channels=1, drop_rate=0, img_size=(160, 160), data_parallel=True,
+                 continuous_latent_dim=100, disc_latent_dim=10, sample_temperature=0.67, small_input=False,
+                 compute_dtype="bf16", rng="host"):
+        super(VariationalAutoEncoder, self).__init__()
+        # wideresnet-D-W, preactresnet18 / 34; densenet and the bottleneck PreActResNets exist in the reference (vae.py:93-104) but
+        # are not built: NotImplementedError, the reference's fall-through error type (vae.py:106); an unknown preactresnet* name
+        # is the reference's KeyError (preactresnet.py:131)
+        encoder_family(encoder_name)
+        drop_rate = check_drop_rate(drop_rate)
+        if not small_input:
+            raise NotImplementedError("small_input=False (7x7 stem + max-pool) is not implemented; the "
+                                      "CIFAR/SVHN configs of main_shot_vae.py use small_input=True")
+        if tuple(img_size) != (32, 32):
+            raise NotImplementedError("only 32x32 inputs are implemented")
+        plan = Plan(encoder_name, in_ch=num_input_channels, img=img_size[0], ldc=continuous_latent_dim,
+                    K=int(disc_latent_dim), drop_rate=drop_rate)
+        self._init_flat(plan, compute_dtype, data_parallel, rng, drop_rate)
+        self._temperature = sample_temperature
+        self._disc_latent_dim = disc_latent_dim
+        self._engine.init_default()
+        self._build_tree()
+        self.feature_extractor.num_feature_channel = plan.cfeat
+
+    # ------------------------------------------------------------------ reference API
     def _draw_noise(self, B, dev, gumbel):
         """noise in the reference's order: randn for z (vae.py:37,82), then rand for gumbel (vae.py:52,69).  With dropout in
         training mode the forward's key comes first (the encoder runs before the sampler, vae.py:140-151): (eps, u, key)"""
