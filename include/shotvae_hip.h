@@ -362,6 +362,41 @@ int sv_sample_bwd(int dtype, const void* dlatent, const float* ls, const float* 
                   int mode, float temperature, int B, int ldc, int K, int Lpad,
                   float* dmu, float* dls, float* dla, void* stream);
 
+/* ---- inference: the decoder's input from a counter-based normal stream, and the decoder's output as an image (latent.hip).
+ * Added under ABI 8: new symbols only, no struct or signature changed.  Both validate their arguments before any HIP call
+ * (null pointers, non-positive sizes, Lpad < ldc + K, unknown mode / dtype: SV_E_ARG / SV_E_SHAPE, nothing launched), take a
+ * stream and allocate nothing: they can be captured into a hipGraph.
+ *
+ * sv_latent_draw writes latent [B][Lpad] of `dtype` = [z | c | 0-pad] (sv_sample_fwd's layout; the pad columns are zeroed) and,
+ * if z_out is not NULL, the fp32 z as [B][ldc]; the latent's z is that fp32 value rounded once.  ldc is arbitrary (not
+ * necessarily a multiple of 4).
+ *   z[b][d] = (mu ? mu[b][d] : 0) + (tau * (ls ? expf(ls[b][d]) : 1)) * n(row0 + b, d)          mu, ls: [B][ldc] fp32 or NULL
+ * n(row, d), a standard normal that depends only on (key, row, d) -- rows row0 .. row0 + B - 1 drawn in one call equal the same
+ * rows drawn in several calls, bit for bit:
+ *   key  = *key, an int64 read FROM DEVICE MEMORY (a captured graph is replayed with another key by writing it there);
+ *          key == NULL: n = 0 and z[b][d] = (mu ? mu[b][d] : 0) exactly, the posterior mean;
+ *   r[0..3] = Philox-4x32-10(counter = (low32(row), high32(row), d >> 2, SV_LATENT_PHILOX_TAG), key = (low32(key), high32(key)))
+ *          -- the generator of the dropout masks, whose fourth counter word is 0: the streams are disjoint;
+ *   p = (d >> 1) & 1,   u1 = ((r[2p] >> 8) + 1) * 2^-24  in (0, 1],   u2 = (r[2p + 1] >> 8) * 2^-24  in [0, 1)   (exact in fp32)
+ *   rad = sqrtf(-2 * logf(u1)),   ang = (float)(2 pi) * u2,   n = (d & 1) ? rad * sinf(ang) : rad * cosf(ang)      (Box-Muller)
+ *          -- one generator call serves the four columns 4j .. 4j + 3: words 0, 1 columns 4j, 4j + 1; words 2, 3 the other two;
+ *          u1 > 0, so every n is finite (|n| <= sqrt(48 ln 2) = 5.77).
+ * The class part c [K], by `mode`:
+ *   0  one-hot of label[b] (int64 [B]); a label outside [0, K) gives an all-zero class part;
+ *   1  a copy of cls[b] (fp32 [B][K]), a soft class vector;
+ *   2  one-hot of argmax_k cls[b][k]; the lowest index wins ties; NaN entries never win (a row of NaNs only: all zero).
+ * tau must be finite and >= 0, row0 >= 0.                                                                                   */
+#define SV_LATENT_PHILOX_TAG 0x4C41544Eu
+int sv_latent_draw(int dtype, const float* mu, const float* ls, const int64_t* key, float tau, int64_t row0, int mode,
+                   const int64_t* label, const float* cls, int B, int ldc, int K, int Lpad, void* latent, float* z_out,
+                   void* stream);
+/* sv_image_out reads NHWC `dtype` [B][H][W][ld] (first C channels: the last ConvTranspose's output) and writes either or both of
+ *   out_f32  NCHW fp32 [B][C][H][W]: the raw values x (sigmoid = 0, exact) or s = 1 / (1 + expf(-x)) (sigmoid = 1);
+ *   out_u8   NHWC uint8 [B][H][W][C] = floorf(255 * s + 0.5): the byte layout sv_augment reads, so generated images can be fed back
+ * (the torch.sigmoid of main_shot_vae.py:381 and the layout change in one pass).  At least one output is required.            */
+int sv_image_out(int dtype, const void* in, int B, int C, int H, int W, int ld, int sigmoid, float* out_f32, uint8_t* out_u8,
+                 void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

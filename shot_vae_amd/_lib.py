@@ -142,6 +142,8 @@ _PROTOS = {
     "sv_ce_bwd": [P, P, I, I, P, P, P],
     "sv_sample_fwd": [I, P, P, P, P, P, P, P, F, P, I, F, I, I, I, I, P, P, P],
     "sv_sample_bwd": [I, P, P, P, P, I, F, I, I, I, I, P, P, P, P],
+    "sv_latent_draw": [I, P, P, P, F, I64, I, P, P, I, I, I, I, P, P, P],
+    "sv_image_out": [I, P, I, I, I, I, I, I, P, P, P],
     "sv_elbo_fwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P],
     "sv_elbo_bwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P, P, P, P, P],
     "sv_cls_fwd": [P, P, P, I, I, P, P],

@@ -925,6 +925,52 @@ class Engine:
                p.cfeat, p.cfeat, _vp(feat.data_ptr()), G, st)
         return feat, prot
 
+    def _decoder_forward(self, fs, f, latent, Gd):
+        """The decoder (decoder.py:12-58) of the forward whose scratch is `fs`, from its input `latent` [G * B, Lpad] in the compute
+        dtype: six ConvTranspose layers, BatchNorm + ReLU between them; the last one for the first Gd groups only.  Fills f.h (the
+        layers' NHWC outputs; f.h[5] is the reconstruction's logits, None if Gd == 0), f.dpro, f.ha.  Shared by forward() and
+        decode()."""
+        p = self.plan
+        B, G = f.B, f.G
+        Bt = B * G
+        dev = latent.device
+        T = self.tdtype
+        st = self._stream()
+        pk, es = self.packs.data_ptr(), self.packs.element_size()
+        finalize, sptr = fs.finalize, fs.sptr
+        f.h = []
+        x = latent.view(Bt, 1, 1, p.Lpad)
+        pro = None
+        f.dpro = []
+        f.ha = {}
+        for i, cv in enumerate(p.dec_convs):
+            ho = cv.Hout
+            gl = G if i < 5 else Gd        # the last ConvTranspose (no BatchNorm behind it): only where rec is needed
+            if gl == 0:                    # a launch of mixed forwards only (the --om / ragged schedules): no reconstruction
+                f.h.append(None)
+                continue
+            out = torch.empty(gl * B, ho, ho, cv.N, dtype=T, device=dev)
+            if pro is not None and self.materialize_decoder_act and cv.Hin <= self.materialize_max_hin:
+                # weight-heavy layers (1x1 ... 4x4 maps, 1024 ... 256 channels): BatchNorm + ReLU once, as a pass over a few
+                # MB, and a prologue-free GEMM (the LDS-DMA loader) -- fused, the transform was redone per channel tile
+                xa = torch.empty_like(x)
+                L.call("sv_bn_act", self.code, _vp(x.data_ptr()), _vp(pro[0]), _vp(pro[1]), pro[2], B * cv.Hin * cv.Hin, cv.Cin,
+                       _vp(xa.data_ptr()), G, st)
+                f.ha[i] = xa
+                self._igemm(cv.geom_fwd(B), xa, pk + es * cv.fwd_off, out, stats=sptr("h%d" % i), tag="fwd:dec%d" % i, groups=gl)
+            else:
+                self._igemm(cv.geom_fwd(B), x, pk + es * cv.fwd_off, out, pro=pro,
+                            stats=sptr("h%d" % i) if i < 5 else None, tag="fwd:dec%d" % i, groups=gl)
+            f.h.append(out)
+            if i < 5:
+                # (consumed by the next layer's sv_igemm prologue -- folded -- unless that layer takes the materialised form, or
+                #  is the last ConvTranspose of a launch that runs it for the reconstructed groups only: the running statistics
+                #  need the mean / rstd of EVERY group)
+                pro = finalize(p.dec_bns[i], "h%d" % i, B * ho * ho,
+                               fold=not (self.materialize_decoder_act and p.dec_convs[i + 1].Hin <= self.materialize_max_hin) and (i < 4 or Gd == G))
+                f.dpro.append(pro[:3])
+                x = out
+
     def _finish_forward(self, fs, f, training, update_order):
         """the running-statistic update of a training forward: deferred into its slot (apply_pending), applied at once without one"""
         if training:
@@ -1007,39 +1053,7 @@ class Engine:
                    0.0 if torch.is_tensor(lam) else float(lam), _vp(lam.data_ptr()) if torch.is_tensor(lam) else None,
                    mode, float(temperature), B, p.ldc, p.K, p.Lpad, _vp(latent[r0:].data_ptr()),
                    _vp(csoft[r0:].data_ptr()), st)
-        # decoder (decoder.py:12-58)
-        f.h = []
-        x = latent.view(Bt, 1, 1, p.Lpad)
-        pro = None
-        f.dpro = []
-        f.ha = {}
-        for i, cv in enumerate(p.dec_convs):
-            ho = cv.Hout
-            gl = G if i < 5 else Gd        # the last ConvTranspose (no BatchNorm behind it): only where rec is needed
-            if gl == 0:                    # a launch of mixed forwards only (the --om / ragged schedules): no reconstruction
-                f.h.append(None)
-                continue
-            out = torch.empty(gl * B, ho, ho, cv.N, dtype=T, device=dev)
-            if pro is not None and self.materialize_decoder_act and cv.Hin <= self.materialize_max_hin:
-                # weight-heavy layers (1x1 ... 4x4 maps, 1024 ... 256 channels): BatchNorm + ReLU once, as a pass over a few
-                # MB, and a prologue-free GEMM (the LDS-DMA loader) -- fused, the transform was redone per channel tile
-                xa = torch.empty_like(x)
-                L.call("sv_bn_act", self.code, _vp(x.data_ptr()), _vp(pro[0]), _vp(pro[1]), pro[2], B * cv.Hin * cv.Hin, cv.Cin,
-                       _vp(xa.data_ptr()), G, st)
-                f.ha[i] = xa
-                self._igemm(cv.geom_fwd(B), xa, pk + es * cv.fwd_off, out, stats=sptr("h%d" % i), tag="fwd:dec%d" % i, groups=gl)
-            else:
-                self._igemm(cv.geom_fwd(B), x, pk + es * cv.fwd_off, out, pro=pro,
-                            stats=sptr("h%d" % i) if i < 5 else None, tag="fwd:dec%d" % i, groups=gl)
-            f.h.append(out)
-            if i < 5:
-                # (consumed by the next layer's sv_igemm prologue -- folded -- unless that layer takes the materialised form, or
-                #  is the last ConvTranspose of a launch that runs it for the reconstructed groups only: the running statistics
-                #  need the mean / rstd of EVERY group)
-                pro = finalize(p.dec_bns[i], "h%d" % i, B * ho * ho,
-                               fold=not (self.materialize_decoder_act and p.dec_convs[i + 1].Hin <= self.materialize_max_hin) and (i < 4 or Gd == G))
-                f.dpro.append(pro[:3])
-                x = out
+        self._decoder_forward(fs, f, latent, Gd)
         rec = None
         if Gd > 0:
             rec = torch.empty(Gd * B, p.in_ch, p.img, p.img, dtype=torch.float32, device=dev)
@@ -1081,6 +1095,104 @@ class Engine:
         f.prot, f.feat = prot, feat
         f.keep = (fs.stats,)
         return logits, f
+
+    # ------------------------------------------------------------------------------- inference (eval mode only)
+    # encode / encoder_map / latent_draw / decode: the halves of an eval-mode forward as calls of their own.  BatchNorm normalises
+    # with the running statistics; none of them touches the running statistics, num_batches_tracked, the pending-update slots or
+    # the gradient buffers, and none keeps a FwdCtx (there is nothing to differentiate).
+
+    def _eval_encoder(self, image):
+        """the encoder of one group in eval mode -> (ctx with .t and the scratch, feat [B, C] fp32, the final BatchNorm's (scale, shift,
+        slope)).  Keep the ctx until every launch that reads the coefficients has been issued."""
+        self._require_gpu(image)
+        self.ensure_packs()
+        image = image.contiguous().float()
+        B = image.shape[0]
+        fs = self._fwd_scratch(B, 1, False, image.device)
+        f = FwdCtx()
+        f.B, f.G, f.training = B, 1, False
+        # `prot` is raw addresses into the scratch: the caller's launches read it, so the scratch lives as long as f (forward() keeps
+        # it the same way) -- freed here, the allocator could hand its memory to the very tensor such a launch writes
+        f.bnbuf, f.bn_off, f.stats = fs.bnbuf, fs.bn_off, fs.stats
+        feat, prot = self._encoder_forward(fs, f, image, None, None, False)
+        return f, feat, prot
+
+    def encode(self, image, want_feat=False):
+        """Encoder + the three inference heads (vae.py:142-146) of an eval-mode forward: no sampler, no decoder launch.  image NCHW
+        fp32 on the device.  Returns (mu [B, ldc], ls [B, ldc], la [B, K]) fp32, and the pooled features [B, C] with want_feat."""
+        p = self.plan
+        _, feat, _ = self._eval_encoder(image)
+        B, dev = feat.shape[0], feat.device
+        mu = torch.empty(B, p.ldc, dtype=torch.float32, device=dev)
+        ls = torch.empty(B, p.ldc, dtype=torch.float32, device=dev)
+        la = torch.empty(B, p.K, dtype=torch.float32, device=dev)
+        L.call("sv_head_fwd", _vp(feat.data_ptr()), B, p.cfeat, _vp(self.param.data_ptr() + 4 * p.head_w_off),
+               _vp(self.param.data_ptr() + 4 * p.head_b_off), p.ldc, p.K, _vp(mu.data_ptr()), _vp(ls.data_ptr()),
+               _vp(la.data_ptr()), self._stream())
+        return (mu, ls, la, feat) if want_feat else (mu, ls, la)
+
+    def encoder_map(self, image):
+        """The encoder's output tensor as the reference's feature_extractor returns it (wideresnet.py:90-91, preactresnet.py:107-109):
+        behind the transition BatchNorm and its activation, NCHW fp32 [B, C, h, h]."""
+        p = self.plan
+        f, _, prot = self._eval_encoder(image)
+        t = f.t[-1]
+        B, h = t.shape[0], t.shape[1]
+        a = torch.empty_like(t)
+        L.call("sv_bn_act", self.code, _vp(t.data_ptr()), _vp(prot[0]), _vp(prot[1]), prot[2], B * h * h, p.cfeat, _vp(a.data_ptr()), 1,
+               self._stream())
+        out = torch.empty(B, p.cfeat, h, h, dtype=torch.float32, device=t.device)
+        L.call("sv_nhwc_to_nchw", self.code, _vp(a.data_ptr()), B, p.cfeat, h, h, p.cfeat, _vp(out.data_ptr()), self._stream())
+        return out
+
+    def latent_draw(self, B, mu=None, ls=None, key=None, tau=1.0, row0=0, label=None, cls=None, argmax=False, want_z=False):
+        """sv_latent_draw: the decoder's input [B, Lpad] in the compute dtype = [z | c | 0-pad], z = mu + tau * exp(ls) * n (mu / ls
+        fp32 [B, ldc] or None: 0 / sigma 1; key: a 1-element int64 DEVICE tensor, None: n = 0), the class part from `label` (int64
+        [B]: one-hot) or `cls` (fp32 [B, K]: copied, or with argmax its one-hot).  Returns latent, or (latent, z fp32) with want_z."""
+        p = self.plan
+        self._require_gpu(self.param)
+        dev = self.param.device
+        for name, t, shape, dt in (("mu", mu, (B, p.ldc), torch.float32), ("ls", ls, (B, p.ldc), torch.float32),
+                                   ("label", label, (B,), torch.int64), ("cls", cls, (B, p.K), torch.float32),
+                                   ("key", key, (1,), torch.int64)):
+            if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape
+                                  or not t.is_contiguous()):
+                raise ValueError("latent_draw: %s must be a contiguous %s device tensor of shape %s" % (name, dt, shape))
+        if (label is None) == (cls is None):
+            raise ValueError("latent_draw: exactly one of label and cls")
+        mode = 0 if label is not None else (2 if argmax else 1)
+        latent = torch.empty(B, p.Lpad, dtype=self.tdtype, device=dev)
+        z = torch.empty(B, p.ldc, dtype=torch.float32, device=dev) if want_z else None
+        ptr = lambda t: _vp(t.data_ptr()) if t is not None else None
+        L.call("sv_latent_draw", self.code, ptr(mu), ptr(ls), ptr(key), float(tau), int(row0), mode, ptr(label), ptr(cls), B, p.ldc,
+               p.K, p.Lpad, _vp(latent.data_ptr()), ptr(z), self._stream())
+        return (latent, z) if want_z else latent
+
+    def decode(self, latent, out="logits"):
+        """The decoder in eval mode from `latent` [B, Lpad] in the compute dtype (latent_draw's / sv_sample_fwd's layout); its last
+        step is sv_image_out.  out: "logits" -> NCHW fp32 raw values, "sigmoid" -> NCHW fp32 sigmoid, "uint8" -> NHWC uint8 pixels
+        [B, H, W, C] (DeviceDataset's layout)."""
+        if out not in ("logits", "sigmoid", "uint8"):
+            raise ValueError("decode: out must be 'logits', 'sigmoid' or 'uint8', not %r" % (out,))
+        p = self.plan
+        self._require_gpu(latent)
+        if latent.dtype != self.tdtype or latent.dim() != 2 or latent.shape[1] != p.Lpad or not latent.is_contiguous():
+            raise ValueError("decode: the latent must be a contiguous [B, %d] %s tensor" % (p.Lpad, self.tdtype))
+        self.ensure_packs()
+        B, dev = latent.shape[0], latent.device
+        fs = self._fwd_scratch(B, 1, False, dev)
+        f = FwdCtx()
+        f.B, f.G, f.training = B, 1, False
+        self._decoder_forward(fs, f, latent, 1)
+        if out == "uint8":
+            img = torch.empty(B, p.img, p.img, p.in_ch, dtype=torch.uint8, device=dev)
+            f32, u8 = None, _vp(img.data_ptr())
+        else:
+            img = torch.empty(B, p.in_ch, p.img, p.img, dtype=torch.float32, device=dev)
+            f32, u8 = _vp(img.data_ptr()), None
+        L.call("sv_image_out", self.code, _vp(f.h[5].data_ptr()), B, p.in_ch, p.img, p.img, p.dec_convs[5].N, int(out == "sigmoid"),
+               f32, u8, self._stream())
+        return img
 
     def backward_classifier(self, f, d_logits):
         """Gradients of forward_classifier's parameters accumulate (+=) into self.grad: sv_fc_bwd, then the shared encoder backward."""

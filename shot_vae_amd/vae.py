@@ -11,9 +11,13 @@ the loop of main_shot_vae.py:261-383 runs unchanged.  Differences (all documente
   * the wideresnet-D-W and preactresnet18 / preactresnet34 encoders on 32x32 inputs are implemented;
   * dropout (``drop_rate``) draws one int64 key per training forward (torch.randint, in front of that forward's
     noise) and regenerates its masks from it in the kernels (shotvae_hip.h, sv_dropout_args): the masks differ from
-    torch's nn.Dropout draws, their distribution does not.
+    torch's nn.Dropout draws, their distribution does not;
+  * in eval mode the halves of the forward are calls of their own (extension): encode / features / predict, decode, reconstruct,
+    generate, and the sub-modules feature_extractor(x) / feature_reconstructor(latent) are callable with the reference's shapes
+    and meaning (vae.py:142,150); the other sub-modules only carry parameters.
 """
 import math
+import weakref
 
 import torch
 from torch import nn
@@ -27,6 +31,22 @@ class _Node(nn.Module):
 
     def forward(self, *a, **k):
         raise RuntimeError("this sub-module is a parameter container; call the VariationalAutoEncoder")
+
+
+class _EntryNode(_Node):
+    """A name-space module that is also callable like the reference's sub-module of that name: the call goes to the method `entry`
+    of the owning model (FlatModule.ENTRY_NODES), looked up when it is called.  The owner is held weakly -- a child that referred to
+    its parent strongly would make a cycle, and the model with its flat device buffers would be freed by the cycle collector only."""
+
+    def __init__(self, owner, entry):
+        super(_EntryNode, self).__init__()
+        self._owner, self._entry = weakref.ref(owner), entry
+
+    def forward(self, *a, **k):
+        owner = self._owner()
+        if owner is None:
+            raise RuntimeError("this sub-module outlived the model it belongs to")
+        return getattr(owner, self._entry)(*a, **k)
 
 
 def _dp_key(key, wrapped):
@@ -88,6 +108,7 @@ class FlatModule(nn.Module):
     WideResNetClassifier (classifier.py)."""
 
     TOP_MODULES = ()          # the reference's top-level sub-modules, in its registration order
+    ENTRY_NODES = {}          # top-level sub-module -> name of the method a call of it runs (the others only carry parameters)
 
     def _init_flat(self, plan, compute_dtype, data_parallel, rng, drop_rate):
         self._plan = plan
@@ -126,7 +147,7 @@ class FlatModule(nn.Module):
     def _build_tree(self):
         eng, plan = self._engine, self._plan
         for name in self.TOP_MODULES:
-            self.add_module(name, _Node())
+            self.add_module(name, _EntryNode(self, self.ENTRY_NODES[name]) if name in self.ENTRY_NODES else _Node())
         for key, kind, payload in plan.state_items():
             k = _dp_key(key, plan.dp_wrapped) if self._data_parallel else key
             parts = k.split(".")
@@ -217,6 +238,8 @@ class FlatModule(nn.Module):
 
 class VariationalAutoEncoder(FlatModule):
     TOP_MODULES = ("feature_extractor", "global_avg", "continuous_inference", "disc_latent_inference", "sample", "feature_reconstructor")
+    # callable with the reference's shapes and meaning (vae.py:142,150), in eval mode
+    ENTRY_NODES = {"feature_extractor": "_feature_extractor", "feature_reconstructor": "_feature_reconstructor"}
 
     def __init__(self, encoder_name, num_input_channels=1, drop_rate=0, img_size=(160, 160), data_parallel=True,
                  continuous_latent_dim=100, disc_latent_dim=10, sample_temperature=0.67, small_input=False,
@@ -328,6 +351,112 @@ class VariationalAutoEncoder(FlatModule):
         self._attach_grads()
         with torch.no_grad():
             self._engine.backward(ctx, d_rec, d_mu, d_ls, d_la, own_grads)
+
+    # ------------------------------------------------------------------ inference API (eval mode only; extension)
+    # The halves of the eval-mode forward as calls of their own (Engine.encode / latent_draw / decode).  BatchNorm normalises with
+    # the running statistics; nothing here updates them or touches the gradients, and no output requires grad.
+
+    def _infer_check(self, what, *tensors):
+        if self.training:
+            raise NotImplementedError("%s is implemented for eval mode only (BatchNorm with the running statistics, no "
+                                      "gradients): call model.eval() first" % what)
+        for t in tensors:
+            if torch.is_tensor(t) and not t.is_cuda:
+                raise L.ShotVaeHipError("VariationalAutoEncoder.%s: input is not on an MI355X (no CPU fallback)" % what)
+
+    def _key_tensor(self, key):
+        """a generator key as sv_latent_draw reads it: a 1-element int64 device tensor (an int is copied to the device)"""
+        if torch.is_tensor(key):
+            if key.dtype != torch.int64 or key.numel() != 1:
+                raise ValueError("key must be an int or a 1-element int64 device tensor")
+            return key.reshape(1)
+        return torch.tensor([int(key)], dtype=torch.int64, device=self._engine.param.device)
+
+    def _class_args(self, c, B):
+        """latent_draw's class arguments of `c`: an int64 label vector [B] or a float class matrix [B, K]"""
+        if c.dtype == torch.int64 and c.dim() == 1 and c.size(0) == B:
+            return dict(label=c.contiguous())
+        if c.is_floating_point() and tuple(c.shape) == (B, self._plan.K):
+            return dict(cls=c.float().contiguous())
+        raise ValueError("the class argument must be an int64 label vector [%d] or a float class matrix [%d, %d]"
+                         % (B, B, self._plan.K))
+
+    def encode(self, image):
+        """(mu [B, ldc], log_sigma [B, ldc], log_alpha [B, K]) of `image`: the encoder and the inference heads only -- what the
+        eval model(image) returns behind its reconstruction, without the sampler, the decoder and the reconstruction's copy."""
+        self._infer_check("encode", image)
+        with torch.no_grad():
+            return self._engine.encode(image)
+
+    def features(self, image):
+        """the pooled encoder features [B, C] (the input of the inference heads, vae.py:143)"""
+        self._infer_check("features", image)
+        with torch.no_grad():
+            return self._engine.encode(image, want_feat=True)[3]
+
+    def predict(self, image):
+        """the predicted class, int64 [B]: argmax of log_alpha, on the device (no host synchronisation)"""
+        self._infer_check("predict", image)
+        with torch.no_grad():
+            return self._engine.encode(image)[2].argmax(dim=1)
+
+    def decode(self, z, c, sigmoid=False):
+        """The decoder's output [B, ch, 32, 32] (raw logits, or their sigmoid) for the continuous latent z [B, ldc] and the class c:
+        an int64 label vector [B] (one-hot; a label outside [0, K) selects no class) or a float class matrix [B, K]."""
+        return self._decode("decode", z, c, sigmoid)
+
+    def _decode(self, what, z, c, sigmoid):
+        self._infer_check(what, z, c)
+        if z.dim() != 2 or z.size(1) != self._plan.ldc:
+            raise ValueError("%s: z must be [B, %d]" % (what, self._plan.ldc))
+        with torch.no_grad():
+            eng = self._engine
+            latent = eng.latent_draw(z.size(0), mu=z.float().contiguous(), **self._class_args(c, z.size(0)))
+            return eng.decode(latent, "sigmoid" if sigmoid else "logits")
+
+    def reconstruct(self, image, label=None, sample=False, key=None):
+        """sigmoid of the reconstruction of `image` from its posterior mean (sample=True: from a posterior sample drawn with `key`,
+        an int or a 1-element int64 device tensor; None: one torch.randint draw, as for a dropout key -- it advances torch's generator) under its predicted class -- or under `label`
+        (int64 [B]): the class-swap "analogy"."""
+        self._infer_check("reconstruct", image, label)
+        with torch.no_grad():
+            eng = self._engine
+            mu, ls, la = eng.encode(image)
+            if sample:
+                key = self._draw_keys(1, image.device) if key is None else self._key_tensor(key)
+            cls = dict(label=label.view(-1).long().contiguous()) if label is not None else dict(cls=la, argmax=True)
+            latent = eng.latent_draw(mu.size(0), mu=mu, ls=ls if sample else None, key=key if sample else None, **cls)
+            return eng.decode(latent, "sigmoid")
+
+    def generate(self, labels, key, tau=1.0, row0=0, dtype="float"):
+        """Class-conditional samples: z ~ N(0, tau^2 I) from the counter-based stream of sv_latent_draw (a sample depends only on
+        key, row0 + its row and the column: a batch drawn in one call equals the same rows drawn in several), c = one-hot(labels)
+        (int64 [B] on the device).  key: an int, or a 1-element int64 device tensor (read on the device: a captured call is
+        replayed with another key by writing it there).  dtype "float": sigmoid images [B, ch, 32, 32] fp32; "uint8": pixels
+        [B, 32, 32, ch] uint8, the layout DeviceDataset takes."""
+        self._infer_check("generate", labels, key)
+        if dtype not in ("float", "uint8"):
+            raise ValueError("generate: dtype must be 'float' or 'uint8'")
+        with torch.no_grad():
+            eng = self._engine
+            labels = labels.view(-1).long().contiguous()
+            latent = eng.latent_draw(labels.size(0), key=self._key_tensor(key), tau=tau, row0=row0, label=labels)
+            return eng.decode(latent, "sigmoid" if dtype == "float" else "uint8")
+
+    def _feature_extractor(self, x):
+        """model.feature_extractor(x): the encoder's output map [B, C, h, h] (behind the transition BatchNorm + activation)"""
+        self._infer_check("feature_extractor", x)
+        with torch.no_grad():
+            return self._engine.encoder_map(x)
+
+    def _feature_reconstructor(self, latent):
+        """model.feature_reconstructor(latent [B, ldc + K, 1, 1]): the decoder's raw logits"""
+        self._infer_check("feature_reconstructor", latent)
+        p = self._plan
+        if latent.dim() != 4 or tuple(latent.shape[1:]) != (p.ldc + p.K, 1, 1):
+            raise ValueError("feature_reconstructor: the latent must be [B, %d, 1, 1]" % (p.ldc + p.K))
+        flat = latent.reshape(latent.size(0), p.ldc + p.K).float()
+        return self._decode("feature_reconstructor", flat[:, :p.ldc].contiguous(), flat[:, p.ldc:].contiguous(), False)
 
     def _run(self, image, groups, eps, u, rec_groups=None, update_order=None, keys=None):
         eng = self._engine
