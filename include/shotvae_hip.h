@@ -397,6 +397,48 @@ int sv_latent_draw(int dtype, const float* mu, const float* ls, const int64_t* k
 int sv_image_out(int dtype, const void* in, int B, int C, int H, int W, int ld, int sigmoid, float* out_f32, uint8_t* out_u8,
                  void* stream);
 
+/* ---- per-image ELBO terms and the importance-weighted bound on log p(x) (score.hip).  Added under ABI 8: new symbols only, no
+ * struct or signature changed.  All three validate their arguments before any HIP call (null pointers, non-positive sizes,
+ * Lpad < ldc + K, unknown dtype / flag, a row range outside the sweep: SV_E_ARG / SV_E_SHAPE, nothing launched), take a stream and
+ * allocate nothing: they can be captured into a hipGraph.  Every sum runs in a fixed order without atomics: bit-reproducible.
+ *
+ * The sweep enumerates the decoder's input rows J = (b * S + s) * Kd + k for image b < B, sample s < S and class row k < Kd, where
+ * Kd = K (label == NULL: every class) or Kd = 1 (label[b], int64 [B]).  sv_latent_sweep writes rows J = j0 .. j0 + R - 1 of it
+ * (a chunk; 0 <= j0, j0 + R <= B * S * Kd) as latent [R][Lpad] of `dtype` = [z_{b,s} | onehot | 0-pad], and lw[b][s] (fp32 [B][S],
+ * the whole array's base is passed; the row with k == 0 writes its entry):
+ *   z[b][s][d] = mu[b][d] + expf(ls[b][d]) * n(row0 + b, s, d)     in fp32; the latent holds that value rounded once to `dtype`
+ *   lw[b][s]   = log p(z) - log q(z | x) = sum_d (n^2 / 2 - z^2 / 2 + ls[b][d])     on the fp32 z and n, summed in double
+ *   onehot     = class k (sweep), or label[b] (a label outside [0, K) gives an all-zero class part, as in sv_latent_draw)
+ * n(row, s, d), a standard normal that depends only on (key, row, s, d):
+ *   r[0..3] = Philox-4x32-10(counter = (low32(row), high32(row), (s << 16) | (d >> 2), SV_SCORE_PHILOX_TAG), key = *key)
+ *   and the word-to-column Box-Muller mapping of sv_latent_draw (above).  S <= 65536 and ldc <= 2^18 keep the two fields of the
+ *   third counter word apart (anything larger: SV_E_SHAPE); the tag differs from SV_LATENT_PHILOX_TAG and from the dropout masks' 0.
+ *   key is an int64 read FROM DEVICE MEMORY; key == NULL: n = 0, z = mu exactly and lw = sum_d (-mu^2 / 2 + ls).
+ * mu, ls: fp32 [B][ldc], both required.  row0 >= 0 is the absolute index of image 0.                                          */
+#define SV_SCORE_PHILOX_TAG 0x53434F52u
+int sv_latent_sweep(int dtype, const float* mu, const float* ls, const int64_t* key, int64_t row0, const int64_t* label, int B, int S,
+                    int K, int ldc, int Lpad, int64_t j0, int R, void* latent, float* lw, void* stream);
+/* sv_recon_rows: nll[j], j < R, the reconstruction term of decoded row j -- NHWC `dtype` rec [R][H][W][ld], first C channels, the
+ * logits r -- against image (j0 + j) / rows_per_image of the NCHW fp32 image [B][C][H][W] (values x); (j0 + R - 1) / rows_per_image
+ * must be < B.
+ *   bce = 1:  sum over C * H * W of  max(r, 0) - r * x + log1pf(expf(-|r|))              (BCE with logits; stable for any finite r)
+ *   bce = 0:  sum of (1 / (1 + expf(-r)) - x)^2, times 1 / (2 x_sigma^2)                  (x_sigma finite and > 0)
+ * Each term in fp32, the sum in double in a fixed order (lib/criterion.py:44-48 on a batch of one).                            */
+int sv_recon_rows(int dtype, const void* rec, const float* image, int B, int64_t j0, int R, int64_t rows_per_image, int C, int H, int W,
+                  int ld, int bce, float x_sigma, float* nll, void* stream);
+/* sv_score_reduce: from nll [B][S][Kd] (Kd = K: the class sweep; Kd = 1: labelled), lw [B][S], la [B][K] (log q(y | x)), mu, ls
+ * [B][ldc] it writes any of the fp32 [B] outputs (NULL skips one; at least one; lw may be NULL without log_px), with q_k = exp(la_k):
+ *   kl_c   = 1/2 sum_d (mu^2 + exp(2 ls) - 2 ls - 1)
+ *   kl_d   = sum_k q_k (la_k + log K)                                                    (a class with q_k = 0 contributes 0)
+ *   recon  = 1/S sum_s sum_k q_k nll[s][k]   (Kd = K; a class with q_k = 0 is skipped: no 0 * inf)   |   1/S sum_s nll[s]  (Kd = 1)
+ *   elbo   = -(recon + kl_c + kl_d)
+ *   log_px = LSE_s( lw[s] + LSE_k(-nll[s][k] - log K) ) - log S + log_px_add   (Kd = K)   |   inner term -nll[s]  (Kd = 1)
+ * LSE is a two-level log-sum-exp about the running maximum: a term of -inf has weight 0, a row of -inf only gives -inf (not NaN), a
+ * term of +inf gives +inf; a NaN in nll, lw or la makes every output it enters NaN (it is never dropped).  One block per image, arithmetic in double.  log_px_add must be finite (MSE mode, normalised:
+ * -(D / 2) log(2 pi x_sigma^2)).                                                                                              */
+int sv_score_reduce(const float* nll, const float* lw, const float* la, const float* mu, const float* ls, int B, int S, int Kd, int K,
+                    int ldc, double log_px_add, float* recon, float* kl_c, float* kl_d, float* elbo, float* log_px, void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

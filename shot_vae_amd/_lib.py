@@ -144,6 +144,9 @@ _PROTOS = {
     "sv_sample_bwd": [I, P, P, P, P, I, F, I, I, I, I, P, P, P, P],
     "sv_latent_draw": [I, P, P, P, F, I64, I, P, P, I, I, I, I, P, P, P],
     "sv_image_out": [I, P, I, I, I, I, I, I, P, P, P],
+    "sv_latent_sweep": [I, P, P, P, I64, P, I, I, I, I, I, I64, I, P, P, P],
+    "sv_recon_rows": [I, P, P, I, I64, I, I64, I, I, I, I, I, F, P, P],
+    "sv_score_reduce": [P, P, P, P, P, I, I, I, I, I, C.c_double, P, P, P, P, P, P],
     "sv_elbo_fwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P],
     "sv_elbo_bwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P, P, P, P, P],
     "sv_cls_fwd": [P, P, P, I, I, P, P],

@@ -214,6 +214,19 @@ __device__ __forceinline__ uint32_t sv_dropout_keep8(uint64_t key, int unit, uin
     }
     return m;
 }
+// Four standard normals from one generator call (sv_latent_draw, sv_latent_sweep; definition in shotvae_hip.h): counter
+// (low32(row), high32(row), c2, tag); Box-Muller on the word pairs (0, 1) and (2, 3): cos, sin of each pair
+__device__ __forceinline__ void sv_normals4(uint64_t key, uint64_t row, uint32_t c2, uint32_t tag, float n[4]) {
+    const sv_u32x4 r = sv_philox4x32_10((uint32_t)row, (uint32_t)(row >> 32), c2, tag, (uint32_t)key, (uint32_t)(key >> 32));
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const float u1 = (float)((r.v[2 * p] >> 8) + 1u) * 0x1p-24f;          // (0, 1]: exact in fp32, log finite
+        const float u2 = (float)(r.v[2 * p + 1] >> 8) * 0x1p-24f;             // [0, 1)
+        const float rad = sqrtf(-2.f * logf(u1)), ang = 6.283185307179586f * u2;
+        n[2 * p] = rad * cosf(ang);
+        n[2 * p + 1] = rad * sinf(ang);
+    }
+}
 // the argument check every dropout entry point runs before it launches (keys, p in (0, 1), thr / scale consistent with p)
 int sv_dropout_check(const sv_dropout_args* a, const char* who);
 

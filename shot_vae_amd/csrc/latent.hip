@@ -8,16 +8,7 @@
 // ------------------------------------------------------------------------------------------ sv_latent_draw
 // the four standard normals of columns 4j .. 4j + 3 of absolute row `row` (shotvae_hip.h: the stream's definition)
 __device__ __forceinline__ void latent_normals4(uint64_t key, uint64_t row, uint32_t j, float n[4]) {
-    const sv_u32x4 r = sv_philox4x32_10((uint32_t)row, (uint32_t)(row >> 32), j, SV_LATENT_PHILOX_TAG, (uint32_t)key,
-                                        (uint32_t)(key >> 32));
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        const float u1 = (float)((r.v[2 * p] >> 8) + 1u) * 0x1p-24f;          // (0, 1]: exact in fp32, log finite
-        const float u2 = (float)(r.v[2 * p + 1] >> 8) * 0x1p-24f;             // [0, 1)
-        const float rad = sqrtf(-2.f * logf(u1)), ang = 6.283185307179586f * u2;
-        n[2 * p] = rad * cosf(ang);
-        n[2 * p + 1] = rad * sinf(ang);
-    }
+    sv_normals4(key, row, j, SV_LATENT_PHILOX_TAG, n);
 }
 
 constexpr int LD_THREADS = 128;

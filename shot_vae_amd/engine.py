@@ -1194,6 +1194,73 @@ class Engine:
                f32, u8, self._stream())
         return img
 
+    # sv_score_reduce's outputs, in the order of its arguments
+    SCORE_OUTPUTS = ("recon", "kl_c", "kl_d", "elbo", "log_px")
+    # decoded rows per chunk of score(): the eval scratch of one chunk is what decode() of that many latents holds -- on
+    # wideresnet-28-2 110880 bytes a row in bf16 and 221760 in fp32 (decoder_row_bytes(); pinned by tests/test_score_cpu.py), so 8192
+    # rows hold 0.91 GB / 1.82 GB: under 1 GB / 2 GB
+    SCORE_CHUNK_ROWS = 8192
+
+    def decoder_row_bytes(self):
+        """bytes of eval scratch one decoded row holds while its chunk is in flight: the six layers' outputs, the materialised
+        activations of the weight-heavy layers and the latent"""
+        p, es = self.plan, 2 if self.code == L.SV_BF16 else 4
+        n = p.Lpad
+        for i, cv in enumerate(p.dec_convs):
+            n += cv.Hout * cv.Hout * cv.N
+            if i > 0 and self.materialize_decoder_act and cv.Hin <= self.materialize_max_hin:
+                n += cv.Hin * cv.Hin * cv.Cin
+        return n * es
+
+    def score(self, image, bce, x_sigma, label=None, samples=1, key=None, row0=0, want=("recon", "kl_c", "kl_d", "elbo"),
+              log_px_add=0.0, chunk_rows=None):
+        """Per-image ELBO terms and / or the importance-weighted bound on log p(x) (shotvae_hip.h: sv_score_reduce) of `image` (NCHW
+        fp32 on the device) in eval mode: encode, then per chunk of at most `chunk_rows` decoded rows sv_latent_sweep -> the decoder
+        -> sv_recon_rows, then sv_score_reduce.  label: int64 [B] (one decoded row per sample) or None (the K class rows per sample);
+        key: a 1-element int64 device tensor, or None (z = mu); row0: the absolute index of image 0 in the sweep's normal stream.
+        Returns a dict of the outputs named in `want` (SCORE_OUTPUTS), fp32 [B] each."""
+        p = self.plan
+        S = int(samples)
+        if S < 1 or S > 65536:
+            raise ValueError("score: samples must be in [1, 65536]")
+        if not want or any(w not in self.SCORE_OUTPUTS for w in want):
+            raise ValueError("score: want must name some of %s" % (self.SCORE_OUTPUTS,))
+        chunk = self.SCORE_CHUNK_ROWS if chunk_rows is None else int(chunk_rows)
+        if chunk < 1:
+            raise ValueError("score: chunk_rows must be >= 1")
+        image = image.contiguous().float()
+        mu, ls, la = self.encode(image)
+        B, dev = mu.shape[0], mu.device
+        for name, t, shape in (("label", label, (B,)), ("key", key, (1,))):
+            if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int64 or tuple(t.shape) != shape
+                                  or not t.is_contiguous()):
+                raise ValueError("score: %s must be a contiguous int64 device tensor of shape %s" % (name, shape))
+        Kd = 1 if label is not None else p.K
+        per = S * Kd
+        total = B * per
+        st = self._stream()
+        ptr = lambda t: _vp(t.data_ptr()) if t is not None else None
+        nll = torch.empty(total, dtype=torch.float32, device=dev)
+        lw = torch.empty(B, S, dtype=torch.float32, device=dev)
+        for j0 in range(0, total, chunk):
+            R = min(chunk, total - j0)
+            latent = torch.empty(R, p.Lpad, dtype=self.tdtype, device=dev)
+            L.call("sv_latent_sweep", self.code, ptr(mu), ptr(ls), ptr(key), int(row0), ptr(label), B, S, p.K, p.ldc, p.Lpad, j0, R,
+                   ptr(latent), ptr(lw), st)
+            # the chunk's scratch (BatchNorm coefficients, read by its launches through raw addresses) and activations live until its
+            # last launch is issued, as in decode(); released then, the next chunk reuses the memory in stream order
+            fs = self._fwd_scratch(R, 1, False, dev)
+            f = FwdCtx()
+            f.B, f.G, f.training = R, 1, False
+            self._decoder_forward(fs, f, latent, 1)
+            L.call("sv_recon_rows", self.code, ptr(f.h[5]), ptr(image), B, j0, R, per, p.in_ch, p.img, p.img, p.dec_convs[5].N, int(bool(bce)),
+                   float(x_sigma), _vp(nll.data_ptr() + 4 * j0), st)
+            del fs, f, latent
+        out = {w: torch.empty(B, dtype=torch.float32, device=dev) for w in want}
+        L.call("sv_score_reduce", ptr(nll), ptr(lw), ptr(la), ptr(mu), ptr(ls), B, S, Kd, p.K, p.ldc, float(log_px_add),
+               *[ptr(out.get(w)) for w in self.SCORE_OUTPUTS], st)
+        return out
+
     def backward_classifier(self, f, d_logits):
         """Gradients of forward_classifier's parameters accumulate (+=) into self.grad: sv_fc_bwd, then the shared encoder backward."""
         self._guarded(self._backward_classifier, f, d_logits)

@@ -7,6 +7,7 @@ disc_log_alpha (:441-447).
 Every per-batch quantity stays on the device (the reference calls float() five times per batch = five host syncs);
 `Evaluator.result()` does the one device-to-host copy of an epoch."""
 import ctypes as C
+import math
 
 import torch
 
@@ -78,3 +79,36 @@ def evaluate(model, elbo_criterion, batches, topk=5):
     for image, label in batches:
         ev.update(image, label)
     return ev.result()
+
+
+def evaluate_scores(model, criterion, batches, samples=0, key=None):
+    """Dataset means of the per-image scores (VariationalAutoEncoder.score_terms): dict(elbo, recon, kl_c, kl_d) at
+    z = mu with samples=0, and with samples > 0 (key: an int or a 1-element int64 device tensor) the same terms over `samples` posterior
+    draws plus log_px and bits_per_dim = -log_px / (D ln 2), D = the elements of one image.  `batches` yields image tensors or
+    (image, ...) tuples on the device.  The model must be in eval mode, as for score() (NotImplementedError otherwise: nothing here
+    switches it), and the dataset must not be empty (ValueError).  An image's draws are indexed by its position in the dataset
+    (row0 = the running image count), so the result does not depend on how the dataset was batched; the sums stay on the device
+    (float64) until the one copy at the end."""
+    samples = int(samples)
+    if samples < 0:
+        raise ValueError("evaluate_scores: samples must be >= 0")
+    if samples > 0 and key is None:
+        raise ValueError("evaluate_scores: samples > 0 needs a key")
+    want = ("elbo", "recon", "kl_c", "kl_d") + (("log_px",) if samples > 0 else ())
+    acc, count, dim = None, 0, 0
+    for batch in batches:
+        image = batch[0] if isinstance(batch, (tuple, list)) else batch
+        if samples > 0 and isinstance(key, int) and not isinstance(key, bool) and image.is_cuda:
+            key = torch.tensor([key], dtype=torch.int64, device=image.device)         # one copy for the whole dataset
+        out = model.score_terms(image, criterion, want, samples=max(samples, 1), key=key if samples > 0 else None, row0=count,
+                                what="evaluate_scores")
+        sums = torch.stack([out[w].double().sum() for w in want])
+        acc = sums if acc is None else acc + sums
+        count += image.size(0)
+        dim = image[0].numel()
+    if acc is None:
+        raise ValueError("evaluate_scores: the dataset is empty")
+    res = dict(zip(want, (acc / count).tolist()))
+    if samples > 0:
+        res["bits_per_dim"] = -res["log_px"] / (dim * math.log(2.0))
+    return res

@@ -16,6 +16,7 @@ the loop of main_shot_vae.py:261-383 runs unchanged.  Differences (all documente
     generate, and the sub-modules feature_extractor(x) / feature_reconstructor(latent) are callable with the reference's shapes
     and meaning (vae.py:142,150); the other sub-modules only carry parameters.
 """
+import collections
 import math
 import weakref
 
@@ -24,6 +25,10 @@ from torch import nn
 
 from . import _lib as L
 from .engine import Engine, Plan, encoder_family
+
+
+# model.score(): the per-image terms of the ELBO, fp32 [B] each; elbo = -(recon + kl_c + kl_d)
+Scores = collections.namedtuple("Scores", ["recon", "kl_c", "kl_d", "elbo"])
 
 
 class _Node(nn.Module):
@@ -442,6 +447,68 @@ class VariationalAutoEncoder(FlatModule):
             labels = labels.view(-1).long().contiguous()
             latent = eng.latent_draw(labels.size(0), key=self._key_tensor(key), tau=tau, row0=row0, label=labels)
             return eng.decode(latent, "sigmoid" if dtype == "float" else "uint8")
+
+    def _score_args(self, what, image, criterion, label, samples, key):
+        """the checks score() and log_likelihood() share -> (label, key) as the engine takes them.  Mode first, then the arguments'
+        values, then where the tensors live: a wrong argument is reported as such on any machine."""
+        self._infer_check(what)
+        p = self._plan
+        if image.dim() != 4 or tuple(image.shape[1:]) != (p.in_ch, p.img, p.img):
+            raise ValueError("%s: the images must be [B, %d, %d, %d]" % (what, p.in_ch, p.img, p.img))
+        samples = int(samples)
+        if samples < 1 or samples > 65536:
+            raise ValueError("%s: samples must be in [1, 65536]" % what)
+        if getattr(criterion, "discrete_dim", p.K) != p.K:
+            raise ValueError("%s: the criterion is built for %d classes, the model for %d" % (what, criterion.discrete_dim, p.K))
+        if not criterion.bce_reconstruction and not float(criterion.x_sigma) > 0:
+            raise ValueError("%s: x_sigma must be > 0" % what)
+        if key is None:
+            if samples != 1:
+                raise ValueError("%s: key=None scores at z = mu, which is one sample; samples=%d needs a key" % (what, samples))
+        elif (key.dtype != torch.int64 or key.numel() != 1) if torch.is_tensor(key) else (isinstance(key, bool) or not isinstance(key, int)):
+            raise ValueError("%s: key must be an int or a 1-element int64 device tensor" % what)
+        if label is not None and (not torch.is_tensor(label) or label.dtype != torch.int64 or label.numel() != image.size(0)):
+            raise ValueError("%s: label must be an int64 vector [%d]" % (what, image.size(0)))
+        self._infer_check(what, image, label, key)
+        return (label.reshape(-1).contiguous() if label is not None else None), (self._key_tensor(key) if key is not None else None)
+
+    def score_terms(self, image, criterion, want, label=None, samples=1, key=None, row0=0, normalised=True, chunk_rows=None,
+                    what="score_terms"):
+        """The outputs named in `want` -- any of "recon", "kl_c", "kl_d", "elbo", "log_px" -- of one pass over `image`, as a dict of
+        fp32 [B] device tensors: what score() and log_likelihood() are made of, for a caller that wants both from the same draws
+        (evaluate_scores).  Arguments as for those two; `what` names the call in error messages."""
+        row0 = int(row0)
+        if row0 < 0:
+            raise ValueError("%s: row0 must be >= 0" % what)
+        label, key = self._score_args(what, image, criterion, label, samples, key)
+        add = 0.0
+        if "log_px" in want and normalised and not criterion.bce_reconstruction:
+            # the normalising constant of the Gaussian likelihood (the Bernoulli likelihood of BCE mode has none)
+            p = self._plan
+            add = -0.5 * p.in_ch * p.img * p.img * math.log(2.0 * math.pi * float(criterion.x_sigma) ** 2)
+        with torch.no_grad():
+            return self._engine.score(image, criterion.bce_reconstruction, criterion.x_sigma, label, samples, key, row0, want=tuple(want),
+                                      log_px_add=add, chunk_rows=chunk_rows)
+
+    def score(self, image, criterion, label=None, samples=1, key=None, row0=0):
+        """Scores(recon, kl_c, kl_d, elbo) of every image, fp32 [B] on the device: the reconstruction term of
+        `criterion` (its bce_reconstruction and x_sigma) averaged over `samples` draws z ~ q(z | x) from the counter-based stream of
+        sv_latent_sweep (key: an int, or a 1-element int64 device tensor, as for generate; an image's draws depend only on key, row0 +
+        its row, the sample and the column) -- or at z = mu exactly with key=None (samples == 1) -- and over the classes: the exact
+        expectation under q(y | x) with label=None, the class label[b] (int64 [B]) otherwise; the two KL terms in closed form."""
+        out = self.score_terms(image, criterion, Scores._fields, label, samples, key, row0, what="score")
+        return Scores(*[out[w] for w in Scores._fields])
+
+    def log_likelihood(self, image, criterion, samples, key, label=None, row0=0, normalised=True, chunk_rows=None):
+        """The importance-weighted bound on log p(x) of every image (log p(x | y = label) with labels), fp32 [B] on the device:
+        log 1/S sum_s p(x | z_s) p(z_s) / q(z_s | x), z_s ~ q(z | x) from the stream of score(), p(x | z) = 1/K sum_k p(x | z, k)
+        (label=None) -- a lower bound in expectation that tightens with `samples`.  The decoder runs over B * S * K rows (B * S with
+        labels) in chunks of at most chunk_rows (default Engine.SCORE_CHUNK_ROWS = 8192: under 1 GB of eval scratch on
+        wideresnet-28-2 in bf16, under 2 GB in fp32).  normalised: MSE mode includes the Gaussian's -(D / 2) log(2 pi x_sigma^2)."""
+        if key is None:
+            raise ValueError("log_likelihood: a key is required (an int or a 1-element int64 device tensor)")
+        return self.score_terms(image, criterion, ("log_px",), label, samples, key, row0, normalised, chunk_rows,
+                                what="log_likelihood")["log_px"]
 
     def _feature_extractor(self, x):
         """model.feature_extractor(x): the encoder's output map [B, C, h, h] (behind the transition BatchNorm + activation)"""
