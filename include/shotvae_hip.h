@@ -552,6 +552,25 @@ int sv_smooth_latent_fwd(int dtype, const void* o, int ldo, const float* eps, co
 int sv_smooth_latent_bwd(int dtype, const void* dlat, int Lpad, const float* dmean, const float* dlogvar, const float* dalpha,
                          const float* logvar, const float* eps, const float* alpha, const float* gs, float temperature,
                          int training, int sample_path, int B, int Dc, int Dd, void* d_o, int ldo, void* stream);
+/* sv_smooth_classify: the classification tail of the encoder -- what Trainer.eval (main_smooth_ELBO_svhn.py:217-226) needs of a
+ * forward, counted on the device.  Added under ABI 8: a new symbol only.  o [B][ldo] of `dtype` is the head GEMM's output as
+ * sv_smooth_latent_fwd reads it, [mean (Dc) | log-variance (Dc) | logits (Dd) | pad]; the pad columns are never read.
+ *   alpha     fp32 [B][Dd] or NULL: softmax(logits) by the very code of sv_smooth_latent_fwd (one device function serves both
+ *             kernels): bit-equal to that kernel's alpha.
+ *   pred      int64 [B] or NULL: the index of the first maximum of that fp32 alpha (the lowest index wins ties: torch.max(alpha, 1)[1]).
+ *             A row whose alpha holds a NaN -- a NaN or +inf logit, or all logits -inf -- gives -1 (sv_smooth_latent_fwd's
+ *             eval-mode one-hot is all zero there).
+ *   label     int64 [B] or NULL; counts and confusion need it.
+ *   counts    int64 [2] or NULL:  counts[0] += #(rows with pred == label),  counts[1] += B.
+ *   confusion int64 [Dd][Dd] or NULL:  confusion[label][pred] += 1 for the rows with both indices in [0, Dd).
+ *             A label outside [0, Dd) or a pred of -1 is a miss: counted in counts[1] and nowhere else.
+ * counts and confusion ACCUMULATE across calls (the caller zeroes them once: a whole test set is evaluated without a host read).
+ * The sums are integer adds -- independent of the block order, bit-reproducible -- with at most one atomic per block and counter
+ * (the rows of a block are combined first).  One wave per row, any Dd.  Validated before any HIP call: o NULL, no output at all,
+ * counts / confusion without label, a non-positive B / Dc / Dd or an unknown dtype give SV_E_ARG, ldo < 2 Dc + Dd SV_E_SHAPE.
+ * Takes a stream and allocates nothing: capturable.                                                                          */
+int sv_smooth_classify(int dtype, const void* o, int ldo, int B, int Dc, int Dd, const int64_t* label, float* alpha, int64_t* pred,
+                       int64_t* counts, int64_t* confusion, void* stream);
 /* reconstruction = tanh(f[..., :C]) of the decoder's NHWC output f [B][H][W][ld] as NCHW fp32 (svhn_vae.py:118-120), and
  * the backward d_f = d_out * (1 - out^2) in NHWC (channels >= C zero)                                                  */
 int sv_tanh_to_nchw(int dtype, const void* f, int B, int C, int H, int W, int ld, float* out, void* stream);

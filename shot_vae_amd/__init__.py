@@ -7,7 +7,7 @@ from .mixup import mixup_vae_data, label_smoothing, optimal_match_index        #
 from .optim import FlatSGD, FlatAdam              # noqa: F401
 from .train import (train_step, train_step_overlapped, train_step_grouped, GraphedTrainStep, DeviceRng, schedule,   # noqa: F401
                     alpha_schedule, m2_train_step, apply_update, inference_kl)
-from .evaluate import Evaluator, evaluate, evaluate_scores       # noqa: F401
+from .evaluate import Evaluator, evaluate, evaluate_scores, SmoothEvaluator, evaluate_smooth       # noqa: F401
 from .classifier import (WideResNetClassifier, get_wide_resnet, CrossEntropyLoss, classifier_train_step,      # noqa: F401
                          GraphedClassifierStep, ClassifierEvaluator, evaluate_classifier)
 from .data import DeviceDataset, ssl_split      # noqa: F401

@@ -167,6 +167,7 @@ _PROTOS = {
     "sv_adam": [P, P, P, P, I64, F, F, F, F, F, P, F, P],
     "sv_smooth_latent_fwd": [I, P, I, P, P, P, F, I, I, I, I, I, P, P, P, P, P, P, P],
     "sv_smooth_latent_bwd": [I, P, I, P, P, P, P, P, P, P, F, I, I, I, I, I, P, I, P],
+    "sv_smooth_classify": [I, P, I, I, I, I, P, P, P, P, P, P],
     "sv_tanh_to_nchw": [I, P, I, I, I, I, I, P, P],
     "sv_tanh_to_nchw_bwd": [I, P, P, I, I, I, I, I, P, P],
     "sv_smooth_elbo_fwd": [P, P, I64, P, P, P, P, I, I, I, C.POINTER(SvSmoothSchedule), P, P, P, P],

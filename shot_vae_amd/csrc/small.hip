@@ -1373,6 +1373,34 @@ __global__ __launch_bounds__(256) void optimal_match_kernel(const float* mu, con
 // discrete code c = one-hot(label) for labelled data, else gs; latent = [z | c | 0] in the compute dtype (the decoder's
 // first GEMM reads it) and in fp32 (API).  One block per sample.
 constexpr float SM_EPS = 1e-12f;
+
+// softmax over the Dd logits of one row by ONE wave (lane l; Dd <= 64 per pass, strided loops cover more): reduce() leaves the
+// row's maximum and the sum of exp(x - max) in every lane, at(x) is the entry of logit x.  smooth_latent_fwd_kernel and
+// smooth_classify_kernel both take alpha from here: the two are bit-equal by construction.
+struct SmoothSoftmax {
+    float mx, se;
+    template <typename T>
+    __device__ __forceinline__ void reduce(const T* logit, int Dd, int l) {
+        mx = -INFINITY;
+        for (int k = l; k < Dd; k += 64) mx = fmaxf(mx, to_f(logit[k]));
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+        se = 0.f;
+        for (int k = l; k < Dd; k += 64) se += expf(to_f(logit[k]) - mx);
+        se = wave_sum(se);
+    }
+    __device__ __forceinline__ float at(float x) const { return expf(x - mx) / se; }
+};
+// argmax over the wave of each lane's (best value, its index): the first maximum; an index of 0x7fffffff = no lane had a candidate
+__device__ __forceinline__ void smooth_wave_argmax(float& abest, int& amax) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const float ov = __shfl_xor(abest, off);
+        const int oi = __shfl_xor(amax, off);
+        if (ov > abest || (ov == abest && oi < amax)) { abest = ov; amax = oi; }
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(64) void smooth_latent_fwd_kernel(const T* o, int ldo, const float* eps, const float* u,
                                                                 const int64_t* label, float temperature, int training, int Dc,
@@ -1390,20 +1418,14 @@ __global__ __launch_bounds__(64) void smooth_latent_fwd_kernel(const T* o, int l
         lat[j] = (T)z;
         l32[j] = z;
     }
-    // softmax over the Dd logits (Dd <= 64 per pass; strided loops cover more)
-    float mx = -INFINITY;
-    for (int k = l; k < Dd; k += 64) mx = fmaxf(mx, to_f(ob[2 * Dc + k]));
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-    float se = 0.f;
-    for (int k = l; k < Dd; k += 64) se += expf(to_f(ob[2 * Dc + k]) - mx);
-    se = wave_sum(se);
+    SmoothSoftmax sm;
+    sm.reduce(ob + 2 * Dc, Dd, l);
     // second pass: alpha and the Gumbel-softmax sample
     float ymx = -INFINITY;
     int amax = 0x7fffffff;
     float abest = -INFINITY;
     for (int k = l; k < Dd; k += 64) {
-        const float a = expf(to_f(ob[2 * Dc + k]) - mx) / se;
+        const float a = sm.at(to_f(ob[2 * Dc + k]));
         alpha[(int64_t)b * Dd + k] = a;
         if (a > abest) { abest = a; amax = k; }
         if (training) {
@@ -1427,12 +1449,7 @@ __global__ __launch_bounds__(64) void smooth_latent_fwd_kernel(const T* o, int l
             gs[(int64_t)b * Dd + k] = expf((logf(a + SM_EPS) + g) / temperature - ymx) / ys;
         }
     } else {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {       // argmax (first maximum)
-            const float ov = __shfl_xor(abest, off);
-            const int oi = __shfl_xor(amax, off);
-            if (ov > abest || (ov == abest && oi < amax)) { abest = ov; amax = oi; }
-        }
+        smooth_wave_argmax(abest, amax);               // argmax (first maximum)
         for (int k = l; k < Dd; k += 64) gs[(int64_t)b * Dd + k] = k == amax ? 1.f : 0.f;
     }
     const int y = label ? (int)label[b] : -1;
@@ -1442,6 +1459,69 @@ __global__ __launch_bounds__(64) void smooth_latent_fwd_kernel(const T* o, int l
         l32[Dc + k] = c;
     }
     for (int k = Dc + Dd + l; k < Lpad; k += 64) lat[k] = (T)0.f;
+}
+
+// The classification tail alone (Trainer.eval, main_smooth_ELBO_svhn.py:217-226): alpha = softmax(logits) as above, pred = its
+// first maximum (-1 for a row whose alpha holds a NaN), and the running hit count / confusion matrix of a test set.  One wave per
+// row, SC_WAVES rows per block; the block's rows meet in LDS and thread 0 issues at most one integer atomic per counter: hits,
+// rows (block 0 alone) and each confusion cell the block's rows touch.  Integer sums: the same bits in any block order.
+constexpr int SC_WAVES = 4;
+template <typename T>
+__global__ __launch_bounds__(64 * SC_WAVES) void smooth_classify_kernel(const T* o, int ldo, int B, int Dc, int Dd,
+                                                                         const int64_t* label, float* alpha, int64_t* pred,
+                                                                         unsigned long long* counts, unsigned long long* confusion) {
+    __shared__ int hit[SC_WAVES];
+    __shared__ int64_t cell[SC_WAVES];                 // label * Dd + pred of the wave's row; -1: not a cell of the matrix
+    const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int b = blockIdx.x * SC_WAVES + w;           // (the same for the whole wave)
+    int my_hit = 0;
+    int64_t my_cell = -1;
+    if (b < B) {
+        const T* lg = o + (int64_t)b * ldo + 2 * Dc;
+        SmoothSoftmax sm;
+        sm.reduce(lg, Dd, l);
+        int amax = 0x7fffffff, nan = 0;
+        float abest = -INFINITY;
+        for (int k = l; k < Dd; k += 64) {
+            const float a = sm.at(to_f(lg[k]));
+            if (alpha) alpha[(int64_t)b * Dd + k] = a;
+            nan |= a != a;
+            if (a > abest) { abest = a; amax = k; }
+        }
+        smooth_wave_argmax(abest, amax);
+        const int p = (__any(nan) || amax >= Dd) ? -1 : amax;
+        if (l == 0) {
+            if (pred) pred[b] = p;
+            if (label) {
+                const int64_t y = label[b];
+                my_hit = p >= 0 && y == p;
+                if (p >= 0 && y >= 0 && y < Dd) my_cell = y * Dd + p;
+            }
+        }
+    }
+    if (!counts && !confusion) return;                 // (kernel arguments: the whole block leaves)
+    if (l == 0) {
+        hit[w] = my_hit;
+        cell[w] = my_cell;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    if (counts) {
+        int h = 0;
+        for (int r = 0; r < SC_WAVES; ++r) h += hit[r];
+        if (h) atomicAdd(&counts[0], (unsigned long long)h);
+        if (blockIdx.x == 0) atomicAdd(&counts[1], (unsigned long long)B);
+    }
+    if (confusion)
+        for (int r = 0; r < SC_WAVES; ++r) {
+            const int64_t c = cell[r];
+            bool first = c >= 0;
+            for (int q = 0; q < r; ++q) first = first && cell[q] != c;
+            if (!first) continue;                      // (no cell, or an earlier row of the block has added this one's share)
+            int n = 1;
+            for (int q = r + 1; q < SC_WAVES; ++q) n += cell[q] == c;
+            atomicAdd(&confusion[c], (unsigned long long)n);
+        }
 }
 
 // backward of the above: d_o = gradient w.r.t. the head GEMM's output row.  dlat: gradient of the (compute-dtype) latent
@@ -2513,6 +2593,22 @@ int sv_smooth_latent_fwd(int dtype, const void* o, int ldo, const float* eps, co
     DISPATCH_T(dtype, hipLaunchKernelGGL((smooth_latent_fwd_kernel<T>), dim3(B), dim3(64), 0, (hipStream_t)stream, (const T*)o, ldo, eps, u,
                                          label, temperature, training, Dc, Dd, Lpad, mean, logvar, alpha, gs, (T*)latent, latent32));
     return sv_check_launch("sv_smooth_latent_fwd");
+}
+
+int sv_smooth_classify(int dtype, const void* o, int ldo, int B, int Dc, int Dd, const int64_t* label, float* alpha, int64_t* pred,
+                       int64_t* counts, int64_t* confusion, void* stream) {
+    SvProfScope prof_scope(stream);
+    SV_REQUIRE(o, SV_E_ARG, "sv_smooth_classify: the head output o is NULL");
+    SV_REQUIRE(alpha || pred || counts || confusion, SV_E_ARG, "sv_smooth_classify: no output (alpha, pred, counts and confusion are all NULL)");
+    SV_REQUIRE(label || (!counts && !confusion), SV_E_ARG, "sv_smooth_classify: counts / confusion need the labels");
+    SV_REQUIRE(B > 0 && Dc > 0 && Dd > 0, SV_E_ARG, "sv_smooth_classify: non-positive size (B=%d Dc=%d Dd=%d)", B, Dc, Dd);
+    SV_REQUIRE((int64_t)ldo >= 2 * (int64_t)Dc + Dd, SV_E_SHAPE, "sv_smooth_classify: ldo=%d < 2 Dc + Dd = %lld", ldo,
+               (long long)(2 * (int64_t)Dc + Dd));
+    SV_REQUIRE(dtype == SV_F32 || dtype == SV_BF16, SV_E_ARG, "sv_smooth_classify: bad dtype %d", dtype);
+    DISPATCH_T(dtype, hipLaunchKernelGGL((smooth_classify_kernel<T>), dim3((B + SC_WAVES - 1) / SC_WAVES), dim3(64 * SC_WAVES), 0,
+                                         (hipStream_t)stream, (const T*)o, ldo, B, Dc, Dd, label, alpha, pred,
+                                         (unsigned long long*)counts, (unsigned long long*)confusion));
+    return sv_check_launch("sv_smooth_classify");
 }
 
 int sv_smooth_latent_bwd(int dtype, const void* dlat, int Lpad, const float* dmean, const float* dlogvar, const float* dalpha,

@@ -9,6 +9,7 @@ Every per-batch quantity stays on the device (the reference calls float() five t
 import ctypes as C
 import math
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -76,6 +77,61 @@ def evaluate(model, elbo_criterion, batches, topk=5):
     """valid() / test(): `batches` yields (image, label) device tensors; returns the result dict.  The reference returns
     (top1, top5) (:458)."""
     ev = Evaluator(model, elbo_criterion, topk)
+    for image, label in batches:
+        ev.update(image, label)
+    return ev.result()
+
+
+class SmoothEvaluator:
+    """Test accuracy of a smooth-ELBO model (SmoothVAE), Trainer.eval of main_smooth_ELBO_svhn.py:217-226: the number of images
+    whose predicted class (first maximum of alpha) is the label, over the number of images.  The two counters -- int64 [2] (hits,
+    images) and the confusion matrix int64 [Dd, Dd], rows = labels -- live on the device and are added to by SmoothVAE.classify
+    (sv_smooth_classify): update() never synchronises (the reference reads every batch back with .cpu().numpy()); result() does
+    the one copy.  The module's mode is not touched: the encoder has no mode-dependent layer.
+
+        ev = SmoothEvaluator(model)
+        for image, label in loader: ev.update(image, label)
+        accuracy = ev.result()["accuracy"]"""
+
+    def __init__(self, model):
+        self.model = model
+        self.reset()
+
+    def reset(self):
+        self.counts = self.confusion = None
+
+    def update(self, image, label):
+        """adds one batch; returns its predictions (int64 [B], on the device)"""
+        if not image.is_cuda or not label.is_cuda:
+            raise L.ShotVaeHipError("SmoothEvaluator: inputs must be on an MI355X (no CPU fallback)")
+        if self.counts is None:
+            Dd = self.model.latent_disc_dim
+            self.counts = torch.zeros(2, dtype=torch.int64, device=image.device)
+            self.confusion = torch.zeros(Dd, Dd, dtype=torch.int64, device=image.device)
+        return self.model.classify(image, label.long(), self.counts, self.confusion)[1]
+
+    def result(self):
+        """dict(accuracy = correct / total (0.0 before any update), correct, total, per_class_accuracy, confusion): Python numbers,
+        and numpy arrays for the last two -- confusion int64 [Dd, Dd] with confusion[label][pred], per_class_accuracy float64 [Dd] =
+        its diagonal over its row sums (NaN for a class without images).  A row without a prediction (NaN logits) or with a label
+        outside [0, Dd) is a miss in `total` and is not in the matrix.  One host synchronisation."""
+        if self.counts is None:
+            return dict(accuracy=0.0, correct=0, total=0, per_class_accuracy=None, confusion=None)
+        Dd = self.confusion.shape[0]
+        flat = torch.cat([self.counts, self.confusion.view(-1)]).cpu().numpy()
+        correct, total = int(flat[0]), int(flat[1])
+        conf = flat[2:].reshape(Dd, Dd).copy()
+        rows = conf.sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            per_class = np.where(rows > 0, np.diag(conf) / np.maximum(rows, 1), np.nan)
+        return dict(accuracy=correct / total if total else 0.0, correct=correct, total=total, per_class_accuracy=per_class,
+                    confusion=conf)
+
+
+def evaluate_smooth(model, batches):
+    """Trainer.eval over `batches` of (image, label) device pairs -> SmoothEvaluator.result().  Integer counts: the result does not
+    depend on how the test set is batched (a ragged last batch included)."""
+    ev = SmoothEvaluator(model)
     for image, label in batches:
         ev.update(image, label)
     return ev.result()

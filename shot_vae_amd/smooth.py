@@ -647,6 +647,116 @@ class SmoothVAE(nn.Module):
         disc_sample = [gs] if label is not None else []      # drawn (and unused) for labelled data, as svhn_vae.py:205-207
         return self._decode_padded(latent), latent_dist, latent_sample, disc_sample
 
+    # ---- inference (extension): no gradients, no noise from torch's generators; the module's mode is neither read nor changed ----
+    @staticmethod
+    def _on_device(what, *tensors):
+        for t in tensors:
+            if torch.is_tensor(t) and not t.is_cuda:
+                raise L.ShotVaeHipError("SmoothVAE.%s: input is not on an MI355X (no CPU fallback)" % what)
+
+    def _label_arg(self, what, label, B):
+        if label is None:
+            return None
+        if not torch.is_tensor(label) or label.dtype != torch.int64 or label.numel() != B:
+            raise ValueError("%s: label must be an int64 vector [%d]" % (what, B))
+        return label.reshape(-1).contiguous()
+
+    def classify(self, x, label=None, counts=None, confusion=None):
+        """-> (alpha [B, Dd] fp32, pred [B] int64): the encoder, the head GEMM and sv_smooth_classify -- no decoder, no noise
+        draw, no host synchronisation.  alpha equals forward's alpha bit for bit; pred is its first maximum (torch.max(alpha,
+        1)[1] of Trainer.eval, main_smooth_ELBO_svhn.py:223), -1 for a row whose alpha holds a NaN.  With `label` (int64 [B]),
+        `counts` (int64 [2]) and / or `confusion` (int64 [Dd, Dd]), caller-owned device tensors, are ADDED to: counts += (rows
+        with pred == label, B), confusion[label][pred] += 1 (shotvae_hip.h: sv_smooth_classify)."""
+        self._on_device("classify", x, label, counts, confusion)
+        B, Dd = x.shape[0], self.latent_disc_dim
+        label = self._label_arg("classify", label, B)
+        if (counts is not None or confusion is not None) and label is None:
+            raise ValueError("classify: counts / confusion need the labels")
+        for t, shape, name in ((counts, (2,), "counts"), (confusion, (Dd, Dd), "confusion")):
+            if t is not None and (t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError("classify: %s must be a contiguous int64 device tensor %s" % (name, list(shape)))
+        with torch.no_grad():
+            self.begin_iteration(x.device)
+            o = self._heads(x)
+            alpha = torch.empty(B, Dd, dtype=torch.float32, device=x.device)
+            pred = torch.empty(B, dtype=torch.int64, device=x.device)
+            L.call("sv_smooth_classify", self._code(), _vp(o), o.shape[-1], B, self.latent_cont_dim, Dd, _vp(label), _vp(alpha),
+                   _vp(pred), _vp(counts), _vp(confusion), _st())
+        return alpha, pred
+
+    def predict(self, x):
+        """the predicted class, int64 [B] on the device: classify(x)[1]"""
+        self._on_device("predict", x)
+        return self.classify(x)[1]
+
+    def reconstruct(self, x, label=None):
+        """[B, C, 32, 32] fp32: the eval-mode forward's reconstruction whatever the module's mode -- z = mean, class =
+        one-hot(label) (int64 [B]; a foreign label gives the class-swap analogy) or one-hot(argmax alpha).  Bit-equal to
+        model.eval(); model(x, label)[0]."""
+        self._on_device("reconstruct", x, label)
+        label = self._label_arg("reconstruct", label, x.shape[0])
+        with torch.no_grad():
+            self.begin_iteration(x.device)
+            latent = _LatentFn.apply(self._heads(x), None, None, label, self.temperature, False, self.latent_cont_dim,
+                                     self.latent_disc_dim, self._L["g1"].Cin, self._code())[4]
+            return self._decode_padded(latent)
+
+    def generate(self, label, key, row0=0, tau=1.0, return_z=False):
+        """Class-conditional samples in [-1, 1] (the Tanh range of the trainers' Normalize(0.5, 0.5)): z[b] = tau * n(row0 + b, .)
+        from the counter-based normal stream of sv_latent_draw, the class one-hot(label) (int64 [B] on the device; a label outside
+        [0, Dd) sets no class).  A row depends only on (key, row0 + b): a batch drawn in one call equals the same rows drawn in
+        several.  key: an int, or a 1-element int64 device tensor -- read on the device, so a captured call is replayed with
+        another key by writing it there.  return_z: -> (images, z [B, Dc] fp32)."""
+        self._on_device("generate", label, key)
+        if not torch.is_tensor(label) or label.dtype != torch.int64:
+            raise ValueError("generate: label must be an int64 vector on the device")
+        label = label.reshape(-1).contiguous()
+        if torch.is_tensor(key):
+            if key.dtype != torch.int64 or key.numel() != 1:
+                raise ValueError("generate: key must be an int or a 1-element int64 device tensor")
+            key = key.reshape(1)
+        else:
+            key = torch.tensor([int(key)], dtype=torch.int64, device=label.device)
+        B, Dc, Dd, Lpad = label.shape[0], self.latent_cont_dim, self.latent_disc_dim, self._L["g1"].Cin
+        with torch.no_grad():
+            latent = torch.empty(B, 1, 1, Lpad, dtype=self._tdt, device=label.device)
+            z = torch.empty(B, Dc, dtype=torch.float32, device=label.device) if return_z else None
+            L.call("sv_latent_draw", self._code(), None, None, _vp(key), float(tau), int(row0), 0, _vp(label), None, B, Dc, Dd, Lpad,
+                   _vp(latent), _vp(z), _st())
+            self.begin_iteration(label.device)
+            img = self._decode_padded(latent)
+        return (img, z) if return_z else img
+
+    def traverse(self, z, label, dim=None, values=None):
+        """Latent traversal -> [B, V, C, 32, 32]: from a base z [B, Dc] fp32 (posterior means, say) and int64 label [B], with `dim`
+        given the continuous dimension `dim` takes each of the V `values` (a sequence or a 1-d tensor) under the class `label`;
+        with dim=None the class sweeps 0 .. Dd - 1 (V = Dd) and `label` is ignored.  The latents are composed with torch (tiny
+        tensors) and decoded in one pass of B * V rows."""
+        Dc, Dd = self.latent_cont_dim, self.latent_disc_dim
+        if z.dim() != 2 or z.shape[1] != Dc:
+            raise ValueError("traverse: z must be [B, %d]" % Dc)
+        B = z.shape[0]
+        if dim is not None:              # (the arguments' values first, then where the tensors live)
+            if values is None or not 0 <= int(dim) < Dc:
+                raise ValueError("traverse: dim must be in [0, %d) and needs the values" % Dc)
+            if label is None:
+                raise ValueError("traverse: a continuous dimension is traversed under the class `label` (int64 [%d])" % B)
+        self._on_device("traverse", z, label, values)
+        with torch.no_grad():
+            z = z.float()
+            if dim is None:
+                V = Dd
+                zz = z[:, None, :].expand(B, V, Dc)
+                cls = torch.eye(Dd, device=z.device)[None].expand(B, V, Dd)
+            else:
+                values = torch.as_tensor(values, dtype=torch.float32, device=z.device).reshape(-1)
+                V = values.numel()
+                zz = z[:, None, :].repeat(1, V, 1)
+                zz[:, :, int(dim)] = values
+                cls = F.one_hot(self._label_arg("traverse", label, B), Dd).float()[:, None, :].expand(B, V, Dd)
+            img = self.decode(torch.cat([zz, cls], dim=2).reshape(B * V, Dc + Dd))
+        return img.view(B, V, *img.shape[1:])
+
 
 svhn_VAE = mnist_VAE = SmoothVAE
 
