@@ -439,6 +439,48 @@ int sv_recon_rows(int dtype, const void* rec, const float* image, int B, int64_t
 int sv_score_reduce(const float* nll, const float* lw, const float* la, const float* mu, const float* ls, int B, int S, int Kd, int K,
                     int ldc, double log_px_add, float* recon, float* kl_c, float* kl_d, float* elbo, float* log_px, void* stream);
 
+/* ---- posterior distances and k-nearest neighbours in latent space (lib/utils/calculate_dist.py) ----------------
+ * Added under ABI 8: new symbols only.  mu and ls are fp32 [rows][D] with row stride D; ls is LOG SIGMA (sigma^2 = exp(ls)^2, the
+ * SHOT-VAE convention; half a smooth model's logvar).  The query comes first in every metric:
+ *   SV_DIST_KL      kl[i][j] = KL(N(q_i) || N(g_j)) = sum_d (ls2 - ls1) + ((sigma1^2 + (mu1 - mu2)^2) / sigma2^2 - 1) / 2
+ *                   (pairwise_norm_kl_dist_gpu)
+ *   SV_DIST_W2      sum_d (mu1 - mu2)^2 + sum_d (sigma1 - sigma2)^2              (pairwise_norm_wasserstein_dist_gpu)
+ *   SV_DIST_EUCLID  sum_d (mu1 - mu2)^2; ls is not read and may be NULL          (pairwise_square_euclidean_gpu)
+ *   SV_DIST_COSINE  mu1 . mu2 / (|mu1|^2 |mu2|^2) -- the reference's formula, SQUARED norms -- a similarity: larger is closer; ls is not
+ *                   read and may be NULL                                        (calculate_mean_dist_pairwise, distance="cosine")
+ * All sums are over the differences themselves (no |a|^2 + |b|^2 - 2 a.b expansion): the Euclid and W2 distance of a row to itself is
+ * exactly 0.  Products in fp32; 16 dimensions are summed in fp32 in index order, the 16-blocks in double in index order: the value of a
+ * pair does not depend on the shape of the problem around it, and sv_pairdist and sv_knn_scan give the same bits for the same pair.
+ *
+ * sv_pairdist: out[i * ldo + j] (fp32, ldo >= N) = the metric of query i and gallery row j.  For small problems and reference parity.
+ *
+ * sv_knn_scan: merges the N gallery rows of this call -- row r has the global index col0 + r -- into the running lists best_val (fp32
+ *   [Q][k]) and best_idx (int64 [Q][k]) of the k closest rows per query, closest first; the [Q][N] matrix is never stored.
+ *   init != 0 empties the lists first (the caller need not initialise them); with init == 0 they are read as an earlier call left them.
+ *   An empty slot is idx = -1 and val = +inf (-inf for the cosine).  Equal values order by the smaller global index.  A NaN value, a
+ *   distance of +inf (a similarity of -inf) and, with self0 >= 0, the global index self0 + i for query i (leave-one-out over a gallery
+ *   that holds the queries) never enter a list.  The lists are the k first pairs of a strict total order on (value, index): after a
+ *   gallery has been scanned they hold the same bits however it was cut into calls.  1 <= k <= 256; any Q, N, D >= 1.
+ *
+ * sv_knn_vote: class votes of every query's neighbours.  A slot votes when 0 <= idx < n_gallery and its label g_label[idx] (int64) is
+ *   in [0, K); its weight is 1 (mode 0), exp(-val / tau) (mode 1: distances) or exp(val / tau) (mode 2: the cosine similarity).
+ *   votes (fp32 [Q][K], optional) = the sums in slot order; pred (int64 [Q], optional) = the first maximum of the votes, -1 when no slot
+ *   voted.  With q_label (int64 [Q]): counts[0] += #(pred == q_label), counts[1] += Q (int64 [2]), confusion[q_label][pred] += 1 (int64
+ *   [K][K]) for the rows with both indices in [0, K) -- the counting rules of sv_smooth_classify: integer atomics only, at most one per
+ *   block and counter, a label outside [0, K) or a pred of -1 is a row and never a hit or a cell, the counters ACCUMULATE across calls.
+ *   best_val may be NULL in mode 0.
+ *
+ * Validated before any HIP call (SV_E_ARG / SV_E_SHAPE, nothing launched): a null pointer, an unknown metric / mode, a NULL ls under KL
+ * or W2, k outside [1, 256], a non-positive size, ldo < N, a negative col0, self0 < -1, tau not finite and > 0 in modes 1 / 2, no
+ * output, counters without q_label.  No float atomics anywhere; each takes a stream and allocates nothing: capturable.              */
+enum { SV_DIST_KL = 0, SV_DIST_W2 = 1, SV_DIST_EUCLID = 2, SV_DIST_COSINE = 3 };
+int sv_pairdist(int metric, const float* q_mu, const float* q_ls, int Q, const float* g_mu, const float* g_ls, int N, int D, float* out,
+                int64_t ldo, void* stream);
+int sv_knn_scan(int metric, const float* q_mu, const float* q_ls, int Q, const float* g_mu, const float* g_ls, int N, int D, int64_t col0,
+                int64_t self0, int k, float* best_val, int64_t* best_idx, int init, void* stream);
+int sv_knn_vote(const float* best_val, const int64_t* best_idx, int Q, int k, const int64_t* g_label, int64_t n_gallery, int K, int mode,
+                float tau, const int64_t* q_label, int64_t* pred, float* votes, int64_t* counts, int64_t* confusion, void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

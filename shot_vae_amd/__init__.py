@@ -7,10 +7,13 @@ from .mixup import mixup_vae_data, label_smoothing, optimal_match_index        #
 from .optim import FlatSGD, FlatAdam              # noqa: F401
 from .train import (train_step, train_step_overlapped, train_step_grouped, GraphedTrainStep, DeviceRng, schedule,   # noqa: F401
                     alpha_schedule, m2_train_step, apply_update, inference_kl)
-from .evaluate import Evaluator, evaluate, evaluate_scores, SmoothEvaluator, evaluate_smooth       # noqa: F401
+from .evaluate import (Evaluator, evaluate, evaluate_scores, SmoothEvaluator, evaluate_smooth, KnnEvaluator,       # noqa: F401
+                       evaluate_knn)
 from .classifier import (WideResNetClassifier, get_wide_resnet, CrossEntropyLoss, classifier_train_step,      # noqa: F401
                          GraphedClassifierStep, ClassifierEvaluator, evaluate_classifier)
 from .data import DeviceDataset, ssl_split      # noqa: F401
 from .smooth import (SmoothVAE, svhn_VAE, mnist_VAE, SmoothELBOLoss, smooth_train_step,      # noqa: F401
                      GraphedSmoothStep)
+from .neighbors import (LatentIndex, encode_posterior, pairwise_distance, pairwise_norm_kl_dist_gpu,      # noqa: F401
+                        pairwise_square_euclidean_gpu, pairwise_norm_wasserstein_dist_gpu, calculate_mean_dist_pairwise)
 from .trace import StepLogger, step_range, enable_ranges     # noqa: F401

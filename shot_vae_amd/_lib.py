@@ -15,6 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 SV_F32, SV_BF16 = 0, 1
 ABI_VERSION = 8                  # include/shotvae_hip.h: SV_ABI_VERSION
 MAX_TAPS, MAX_PHASES = 16, 4
+DIST_KL, DIST_W2, DIST_EUCLID, DIST_COSINE = 0, 1, 2, 3      # include/shotvae_hip.h: SV_DIST_*
 
 
 class SvPhase(C.Structure):
@@ -147,6 +148,9 @@ _PROTOS = {
     "sv_latent_sweep": [I, P, P, P, I64, P, I, I, I, I, I, I64, I, P, P, P],
     "sv_recon_rows": [I, P, P, I, I64, I, I64, I, I, I, I, I, F, P, P],
     "sv_score_reduce": [P, P, P, P, P, I, I, I, I, I, C.c_double, P, P, P, P, P, P],
+    "sv_pairdist": [I, P, P, I, P, P, I, I, P, I64, P],
+    "sv_knn_scan": [I, P, P, I, P, P, I, I, I64, I64, I, P, P, I, P],
+    "sv_knn_vote": [P, P, I, I, P, I64, I, I, F, P, P, P, P, P, P],
     "sv_elbo_fwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P],
     "sv_elbo_bwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P, P, P, P, P],
     "sv_cls_fwd": [P, P, P, I, I, P, P],

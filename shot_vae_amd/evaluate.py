@@ -137,6 +137,64 @@ def evaluate_smooth(model, batches):
     return ev.result()
 
 
+class KnnEvaluator:
+    """k-NN accuracy of a model's latent space: every test image is encoded (neighbors.encode_posterior) and classified by the vote of
+    its k nearest rows of `index` (a neighbors.LatentIndex built with num_classes over the labelled pool).  As in SmoothEvaluator the
+    counters -- int64 [2] (hits, images) and the confusion matrix int64 [K, K], rows = labels -- live on the device and are added to
+    by sv_knn_vote: update() never synchronises, result() does the one copy of a test set.
+
+        ev = KnnEvaluator(model, index, k=20)
+        for image, label in loader: ev.update(image, label)
+        accuracy = ev.result()["accuracy"]"""
+
+    def __init__(self, model, index, k=20, weights="uniform", tau=1.0):
+        if index.num_classes is None:
+            raise ValueError("KnnEvaluator: the index was built without num_classes")
+        self.model, self.index, self.k, self.weights, self.tau = model, index, int(k), weights, float(tau)
+        self.reset()
+
+    def reset(self):
+        self.counts = self.confusion = None
+
+    def update(self, image, label):
+        """adds one batch; returns its predictions (int64 [B], on the device)"""
+        if not image.is_cuda or not label.is_cuda:
+            raise L.ShotVaeHipError("KnnEvaluator: inputs must be on an MI355X (no CPU fallback)")
+        from .neighbors import encode_posterior
+        mu, ls = encode_posterior(self.model, image)
+        if self.counts is None:
+            K = self.index.num_classes
+            self.counts = torch.zeros(2, dtype=torch.int64, device=image.device)
+            self.confusion = torch.zeros(K, K, dtype=torch.int64, device=image.device)
+        return self.index.classify(mu, ls, self.k, weights=self.weights, tau=self.tau, label=label.long(), counts=self.counts,
+                                   confusion=self.confusion)
+
+    result = SmoothEvaluator.result      # the same counters, the same read-out: accuracy, correct, total, per_class_accuracy, confusion
+
+
+def evaluate_knn(model, gallery_batches, test_batches, k=20, metric="kl", weights="uniform", tau=1.0, num_classes=None):
+    """Top-1 k-NN accuracy of the latent space: the posteriors of `gallery_batches` ((image, label) device pairs: the labelled pool)
+    are the gallery, every image of `test_batches` votes among its k nearest under `metric` -> KnnEvaluator.result(): accuracy,
+    correct, total, per_class_accuracy, confusion.  num_classes defaults to the model's number of classes.  The model must be in eval
+    mode (encode_posterior).  Integer counts: the result does not depend on how either set is batched."""
+    from .neighbors import LatentIndex, encode_posterior, _metric
+    _metric(metric)                                                      # an unknown metric fails before any encoding
+    if num_classes is None:
+        num_classes = model.latent_disc_dim if hasattr(model, "latent_disc_dim") else model._plan.K
+    index = None
+    for image, label in gallery_batches:
+        mu, ls = encode_posterior(model, image)
+        if index is None:
+            index = LatentIndex(mu.shape[1], metric=metric, num_classes=num_classes)
+        index.add(mu, ls, label)
+    if index is None:
+        raise ValueError("evaluate_knn: the gallery is empty")
+    ev = KnnEvaluator(model, index, k, weights, tau)
+    for image, label in test_batches:
+        ev.update(image, label)
+    return ev.result()
+
+
 def evaluate_scores(model, criterion, batches, samples=0, key=None):
     """Dataset means of the per-image scores (VariationalAutoEncoder.score_terms): dict(elbo, recon, kl_c, kl_d) at
     z = mu with samples=0, and with samples > 0 (key: an int or a 1-element int64 device tensor) the same terms over `samples` posterior
