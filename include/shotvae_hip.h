@@ -46,7 +46,16 @@ typedef struct {
 } sv_phase;
 
 /* Geometry of one conv-like layer:  out[b, qy*osy+ooy, qx*osx+oox, n] =
- *     sum_{t,c} act(x[b, qy*sy+dy[t], qx*sx+dx[t], c]) * w[n][t][c]                                  */
+ *     sum_{t,c} act(x[b, qy*sy+dy[t], qx*sx+dx[t], c]) * w[n][t][c]
+ * The leading dimensions (ldx >= Cin, ldo >= N; sv_igemm: ldx % 8 == 0, ldo % 4 == 0; sv_wgrad: both % 8 == 0):
+ *   - Columns [N, ldo) of every output pixel row belong to the caller and are not written.
+ *   - Columns [Cin, ldx) of the input may hold anything and do not influence the result.
+ *   - `residual` and `ex` have the output's layout, including ldo.
+ * So `out = base + c0` with ldo = C_total is a channel-slice write into a wider tensor (the only reason the fields exist); a batched
+ * launch strides its groups by B*Hin*Win*ldx and B*Hout*Wout*ldo elements.  Hin / Win and Hq / Wq are independent and need not be
+ * powers of two: the specialised kernels decline what they do not cover (their *_try guards) and the generic kernels answer.
+ * sv_bwd3x3 alone is restricted: square 8 / 16 / 32-pixel maps, ldx == Cin, ldo == N (SV_E_SHAPE otherwise).
+ * (tests/test_conv_geometry_gpu.py)                                                                                         */
 typedef struct {
     int32_t B, Hin, Win, Cin, ldx;          /* input  tensor [B,Hin,Win,ldx],  Cin  % 16 == 0        */
     int32_t Hq, Wq, sy, sx;                 /* per-phase output grid and input stride                */

@@ -239,6 +239,33 @@ print("ASAN_DRIVE_OK", n_ok, n_err)
     assert n_ok >= 100, r.stdout
 
 
+@pytest.mark.parametrize("what", ["rect", "ldo", "ldx"])
+def test_bwd3x3_refuses_off_model_geometry(what):
+    """sv_bwd3x3 covers square 8 / 16 / 32-pixel maps with dense leading dimensions.  An 8 x 16 map, ldo = N + 8 and ldx = Cin + 8
+    are refused by its own shape check (SV_E_SHAPE, before any HIP call: no device needed) and dw, out and bsums -- host buffers
+    here -- keep their contents."""
+    from shot_vae_amd import geometry as G
+    B, Cc = 4, 32
+    g = {"rect": lambda: G.convT_like(B, 8, 16, Cc, Cc, 3, 1, 1), "ldo": lambda: G.convT_like(B, 16, 16, Cc, Cc, 3, 1, 1, ldo=Cc + 8),
+         "ldx": lambda: G.convT_like(B, 16, 16, Cc, Cc, 3, 1, 1, ldx=Cc + 8)}[what]()
+    n = B * g.Hout * g.Wout * max(g.ldo, g.ldx)
+    out, dw, bsums = (ctypes.c_uint16 * n)(*([0x40E0] * n)), (ctypes.c_float * (9 * Cc * Cc))(*([7.0] * (9 * Cc * Cc))), (ctypes.c_double * (8 * Cc))(*([7.0] * (8 * Cc)))
+    src, vec, ws = (ctypes.c_uint16 * n)(), (ctypes.c_float * Cc)(), (ctypes.c_float * 16)()
+    a = L.SvBwd3x3Args()
+    a.dy = a.x = a.w = ctypes.addressof(src)
+    a.out, a.dw, a.bsums, a.ws = ctypes.addressof(out), ctypes.addressof(dw), ctypes.addressof(bsums), ctypes.addressof(ws)
+    a.x_scale = a.x_shift = a.x_mean = a.x_rstd = ctypes.addressof(vec)
+    a.x_slope, a.replicas, a.groups, a.ws_elems = 0.01, 4, 1, 1 << 24
+    lib = L.lib()
+    assert lib.sv_bwd3x3(ctypes.byref(g), L.SV_BF16, ctypes.byref(a), None) == -2          # SV_E_SHAPE
+    assert b"sv_bwd3x3: stride-1 3x3 layers" in lib.sv_last_error()
+    assert all(v == 0x40E0 for v in out) and all(v == 7.0 for v in dw) and all(v == 7.0 for v in bsums)
+    # the same arguments on the layer's own geometry pass the shape check (and stop at the next one: the workspace is a stub)
+    a.ws_elems = 16
+    assert lib.sv_bwd3x3(ctypes.byref(G.convT_like(B, 16, 16, Cc, Cc, 3, 1, 1)), L.SV_BF16, ctypes.byref(a), None) == -1
+    assert b"workspace" in lib.sv_last_error()
+
+
 def test_asm_mfma_lint_parser():
     """tools/asm_mfma_lint.py on synthetic ISA: a VALU write of an MFMA operand with fewer than two wait states in between is
     reported, the same write followed by `s_nop 1` (or by two other instructions) is not; register RANGES count."""

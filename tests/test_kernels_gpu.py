@@ -65,14 +65,35 @@ def repack(master, g, transpose, dt):
     return dst
 
 
-def run_igemm(g, dt, x, w, pro=None, bias=None, residual=None, stats=False, ex=None):
+SENTINEL = 7.0       # what run_igemm fills the output allocation with (exact in bf16)
+
+
+def pad_channels(t, ld, fill=float("nan")):
+    """t [..., C] -> [..., ld]: columns [C, ld) hold `fill` (NaN: whatever reads them shows up in the result)"""
+    if t.shape[-1] == ld:
+        return t
+    o = torch.full(t.shape[:-1] + (ld,), fill, dtype=t.dtype)
+    o[..., :t.shape[-1]] = t
+    return o
+
+
+def run_igemm(g, dt, x, w, pro=None, bias=None, residual=None, stats=False, ex=None, groups=1, sparse_out=0, info=None):
+    """One sv_igemm launch on CPU operands.  x / residual / ex["x"] are dense NHWC tensors ([groups * B, ...]); where the geometry's
+    ldx / ldo are wider than their channel count they are padded with NaN columns.  Returns the whole output [groups * B, Hout, Wout,
+    ldo] and the sums ([2N], or [groups][2N] for a batched launch).  With `info` (a dict) the output lies inside a larger allocation,
+    a band of at least one image of SENTINEL elements on either side of it: info["lo"] / info["hi"] return the bands, and
+    info["blocks"] the grid sv_igemm_query_blocks reports for the launch."""
     code, tdt, _ = DT[dt]
     d = dev()
-    xd = x.to(d, tdt).contiguous()
-    out = torch.full((g.B, g.Hout, g.Wout, g.ldo), 7.0, dtype=tdt, device=d)
+    xd = pad_channels(x, g.ldx).to(d, tdt).contiguous()
+    rows = groups * g.B * g.Hout * g.Wout
+    band = 0 if info is None else (2 * g.Hout * g.Wout + 7) // 8 * 8        # (a multiple of 8 rows: the output keeps 16-byte alignment)
+    buf = torch.full(((rows + 2 * band) * g.ldo,), SENTINEL, dtype=tdt, device=d)
+    out = buf[band * g.ldo:(band + rows) * g.ldo].view(groups * g.B, g.Hout, g.Wout, g.ldo)
     a = L.SvIgemmArgs()
-    keep = [xd, out, w]
+    keep = [xd, buf, w]
     a.x, a.w, a.out = xd.data_ptr(), w.data_ptr(), out.data_ptr()
+    a.groups, a.sparse_out = (groups if groups > 1 else 0), sparse_out
     if pro is not None:
         sc, sh = pro[0].to(d).float().contiguous(), pro[1].to(d).float().contiguous()
         keep += [sc, sh]
@@ -82,25 +103,34 @@ def run_igemm(g, dt, x, w, pro=None, bias=None, residual=None, stats=False, ex=N
         keep.append(bd)
         a.bias = bd.data_ptr()
     if residual is not None:
-        rd = residual.to(d, tdt).contiguous()
+        rd = pad_channels(residual, g.ldo).to(d, tdt).contiguous()
         keep.append(rd)
         a.residual = rd.data_ptr()
     sums = None
     R = 4      # replicated accumulators: block b adds to copy b % R
     a.replicas = R
     if stats:
-        sums = torch.zeros(R, 2 * g.N, device=d, dtype=ACC)
+        sums = torch.zeros(groups, R, 2 * g.N, device=d, dtype=ACC)
         a.stats = sums.data_ptr()
     if ex is not None:
-        exd = ex["x"].to(d, tdt).contiguous()
+        exd = pad_channels(ex["x"], g.ldo).to(d, tdt).contiguous()
         vec = [ex[k].to(d).float().contiguous() for k in ("scale", "shift", "mean", "rstd")]
         keep += [exd] + vec
-        sums = torch.zeros(R, 2 * g.N, device=d, dtype=ACC)
+        sums = torch.zeros(groups, R, 2 * g.N, device=d, dtype=ACC)
         a.ex, a.ex_scale, a.ex_shift, a.ex_mean, a.ex_rstd = [t.data_ptr() for t in [exd] + vec]
         a.ex_slope, a.bsums = ex["slope"], sums.data_ptr()
+    if info is not None:
+        blocks = C.c_int(-1)
+        L.call("sv_igemm_query_blocks", C.byref(g), code, C.byref(a), C.byref(blocks))
+        info["blocks"] = blocks.value
     L.call("sv_igemm", C.byref(g), code, C.byref(a), st())
     torch.cuda.synchronize()
-    return out.float().cpu(), (None if sums is None else sums.sum(0).float().cpu())
+    if info is not None:
+        info["lo"], info["hi"] = buf[:band * g.ldo].float().cpu(), buf[(band + rows) * g.ldo:].float().cpu()
+    if sums is not None:
+        sums = sums.sum(1).float().cpu()
+        sums = sums[0] if groups == 1 else sums
+    return out.float().cpu(), sums
 
 
 def bq(t, dt):
