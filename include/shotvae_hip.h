@@ -490,6 +490,48 @@ int sv_knn_scan(int metric, const float* q_mu, const float* q_ls, int Q, const f
 int sv_knn_vote(const float* best_val, const int64_t* best_idx, int Q, int k, const int64_t* g_label, int64_t n_gallery, int K, int mode,
                 float tau, const int64_t* q_label, int64_t* pred, float* votes, int64_t* counts, int64_t* confusion, void* stream);
 
+/* ---- the aggregate posterior q(z) = 1/N sum_j q(z | x_j) of a gallery of posteriors (aggpost.hip) ---------------
+ * Added under ABI 8: new symbols only.  mu, ls, z are fp32 [rows][D] with row stride D; ls is LOG SIGMA, as in the sections above.
+ *
+ * sv_aggpost_sample: for query row i < Q and the sample index s,
+ *   z[i][d] = mu[i][d] + expf(ls[i][d]) * n(row0 + i, s, d)      n: THE STREAM OF sv_latent_sweep (tag SV_SCORE_PHILOX_TAG, counter
+ *             (low32(row), high32(row), (s << 16) | (d >> 2), tag), the same Box-Muller mapping; 0 <= s < 65536, D <= 2^18, anything
+ *             larger: SV_E_SHAPE), so that (key, row, s) gives the sample score(samples = S, key = ...) uses; key (int64 in device
+ *             memory) == NULL: n = 0 and z = mu exactly
+ *   lqx[i]  = log q(z_i | x_i) = sum_d (-n^2 / 2 - ls) - D/2 log(2 pi)
+ *   lpz[i]  = log p(z_i)       = sum_d (-z^2 / 2)      - D/2 log(2 pi)       terms in fp32, sums in double in index order; fp32 [Q]
+ *
+ * sv_aggpost_scan: the joint density.  The value of query i and gallery row j is
+ *   v(i, j) = -1/2 sum_d (z_id - mu_jd)^2 exp(-2 ls_jd) - sum_d ls_jd - D/2 log(2 pi)          (= log N(z_i; mu_j, sigma_j^2))
+ *   by sv_pairdist's one-value-per-pair rule: direct differences, 16 dimensions summed in fp32 with explicit fmaf in index order
+ *   (fmaf((z - mu) * (z - mu), expf(-2 ls), sum)), the 16-blocks and the row scalar sum_d ls summed in double.
+ *   A partial state is a running maximum m and s = sum exp(v - m) over the gallery rows merged into it so far: m, s double [P][Q].
+ *   init != 0 empties the states first (m = -inf, s = 0; the caller need not initialise them); with init == 0 they are read as an
+ *   earlier call left them.  The N rows of this call -- row r has the global index col0 + r -- are dealt to the P partial states in
+ *   tiles of 64 rows (tile t to state t mod P): a fixed function of the arguments.  With self0 >= 0 the pair col0 + r == self0 + i is
+ *   skipped (leave-one-out).  A term of -inf has weight 0; a term of +inf makes the state +inf; a NaN pair value makes that query's
+ *   state NaN (m = NaN): it is never dropped.  1 <= P <= 64; P = 1 is valid.
+ *
+ * sv_aggpost_dims: the per-dimension marginals: the same arguments with states [P][Q][D] and, per (i, d), the fp32 term
+ *   v_d(i, j) = fmaf((z_id - mu_jd)^2, -0.5f * expf(-2 ls_jd), -ls_jd - (float)(log(2 pi) / 2))
+ *   -- one online log-sum-exp per (i, d), no sum over d.  The maximum is kept in fp32 (exact), the sum in double; a term's weight is
+ *   exp(v - m) evaluated in fp32.  Rows are dealt to the states as in the scan; D <= 2^22.
+ *
+ * sv_aggpost_finish: out[r] = M + log(sum_p s_p exp(m_p - M)) - log(count), M = max_p m_p, for r < R over the states m, s [P][R]; in
+ *   double, the partials in index order, rounded once to fp32.  A row whose partials are all empty gives -inf (not NaN), a +inf stays
+ *   +inf, a NaN stays NaN.  R = Q serves the scan, R = Q * D the dims.
+ *
+ * Validated before any HIP call (SV_E_ARG / SV_E_SHAPE, nothing launched): a null pointer (key excepted), a non-positive size, a
+ * negative col0 or row0, self0 < -1, s < 0, P outside [1, 64], count < 1.  Each takes a stream and allocates nothing: capturable.  No
+ * atomics: two runs of the same call sequence give the same bits.                                                                  */
+int sv_aggpost_sample(const float* mu, const float* ls, const int64_t* key, int64_t row0, int s, int Q, int D, float* z, float* lqx,
+                      float* lpz, void* stream);
+int sv_aggpost_scan(const float* z, int Q, const float* g_mu, const float* g_ls, int N, int D, int64_t col0, int64_t self0, double* m,
+                    double* s, int P, int init, void* stream);
+int sv_aggpost_dims(const float* z, int Q, const float* g_mu, const float* g_ls, int N, int D, int64_t col0, int64_t self0, double* m,
+                    double* s, int P, int init, void* stream);
+int sv_aggpost_finish(const double* m, const double* s, int P, int64_t R, int64_t count, float* out, void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <math.h>
 #include "shotvae_hip.h"
 
 typedef __bf16 bf16;
@@ -244,6 +245,72 @@ __device__ __forceinline__ int sv_window_slot(int NC, int group, int bx) {
         if (y < xcd) prefix += cnt;
     }
     return prefix + ((bx - ((xcd - l0) & 7)) >> 3);
+}
+
+// ---- log-sum-exp state (score.hip, aggpost.hip) ---------------------------------------------------------------------------
+// (m, a): the value m + log(a) with m the running maximum; a term of -inf has weight 0; m = +inf is absorbing; a NaN term makes the
+// result NaN (fmax alone would drop it)
+struct ScoreLse { double m, a; };
+__device__ __forceinline__ ScoreLse score_lse_merge(ScoreLse p, ScoreLse q) {
+    if (p.m != p.m || q.m != q.m) return ScoreLse{NAN, 0.0};
+    const double m = fmax(p.m, q.m);
+    if (!(m > -INFINITY) || !(m < INFINITY)) return ScoreLse{m, m == INFINITY ? 1.0 : 0.0};    // all -inf so far, or +inf (or NaN)
+    return ScoreLse{m, p.a * exp(p.m - m) + q.a * exp(q.m - m)};                                // exp(-inf - m) = 0
+}
+__device__ __forceinline__ double score_lse_value(ScoreLse p) { return (p.m > -INFINITY && p.m < INFINITY) ? p.m + log(p.a) : p.m; }
+
+// ---- posterior tiles (knn.hip, aggpost.hip): 64 gallery rows x 16 dimensions per staged chunk, 256 threads ------------------
+constexpr int KN_THREADS = 256;       // 16 x 16 threads; thread (ty, tx) owns rows MQ * ty .., columns 4 * tx .. of the tile
+constexpr int KN_TG = 64;             // gallery rows per tile
+constexpr int KN_DC = 16;             // dimensions per staged chunk
+
+template <int METRIC> struct KnTraits {
+    static constexpr bool TWO = METRIC == SV_DIST_KL || METRIC == SV_DIST_W2;          // a second operand array (from ls)
+    static constexpr bool AUX = METRIC == SV_DIST_KL || METRIC == SV_DIST_COSINE;      // a per-row scalar (sum ls / |mu|^2)
+};
+
+// Staging of rows [r0, r0 + ROWS) x dimensions [d0, d0 + 16), in two halves so that the global loads of the next chunk are in
+// flight while the current one is multiplied: kn_load reads mu (and ls where the metric reads it) into registers -- 16 consecutive
+// threads take the 16 dimensions of one row --, kn_store writes A[d][ROWS + 4] (mu) and B[d][ROWS + 4] (from ls: KL sigma^2 for a query
+// row and 1 / sigma^2 for a gallery row, W2 sigma); rows and dimensions beyond the end are staged as the metric's neutral element.
+// aux[i] (double) gathers the thread's share of the row scalar of its i-th row (KL: sum ls, cosine: |mu|^2) over the chunks;
+// kn_aux_reduce adds the 16 shares of a row with an xor-butterfly (a fixed order).
+template <int METRIC, int ROWS>
+__device__ __forceinline__ void kn_load(const float* __restrict__ mu, const float* __restrict__ ls, int64_t r0, int64_t nrows, int d0,
+                                        int D, float* m, float* l) {
+    const int d = d0 + (threadIdx.x & 15), rr = threadIdx.x >> 4;
+#pragma unroll
+    for (int i = 0; i < ROWS / 16; ++i) {
+        const int64_t gr = r0 + rr + 16 * i;
+        const bool ok = gr < nrows && d < D;
+        m[i] = ok ? mu[gr * D + d] : 0.f;
+        l[i] = (KnTraits<METRIC>::TWO && ok) ? ls[gr * D + d] : 0.f;
+    }
+}
+template <int METRIC, int ROWS, bool GALLERY>
+__device__ __forceinline__ void kn_store(const float* m, const float* l, int64_t r0, int64_t nrows, int d0, int D, float* A, float* B,
+                                         double* aux) {
+    constexpr int LD = ROWS + 4;
+    const int dd = threadIdx.x & 15, rr = threadIdx.x >> 4;
+#pragma unroll
+    for (int i = 0; i < ROWS / 16; ++i) {
+        const int r = rr + 16 * i;
+        const bool ok = r0 + r < nrows && d0 + dd < D;
+        A[dd * LD + r] = m[i];
+        if (METRIC == SV_DIST_KL) {
+            B[dd * LD + r] = ok ? expf(GALLERY ? -2.f * l[i] : 2.f * l[i]) : 0.f;
+            aux[i] += (double)l[i];
+        } else if (METRIC == SV_DIST_W2) {
+            B[dd * LD + r] = ok ? expf(l[i]) : 0.f;
+        } else if (METRIC == SV_DIST_COSINE) {
+            aux[i] += (double)m[i] * (double)m[i];
+        }
+    }
+}
+__device__ __forceinline__ double kn_aux_reduce(double x) {
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) x += __shfl_xor(x, off);
+    return x;
 }
 
 // host side ------------------------------------------------------------------------------------------

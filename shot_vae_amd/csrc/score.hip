@@ -146,16 +146,7 @@ int sv_recon_rows(int dtype, const void* rec, const float* image, int B, int64_t
 // ------------------------------------------------------------------------------------------ sv_score_reduce
 constexpr int SR_THREADS = 256;
 
-// (m, a): the value m + log(a) with m the running maximum; a term of -inf has weight 0; m = +inf is absorbing; a NaN term makes the
-// result NaN (fmax alone would drop it)
-struct ScoreLse { double m, a; };
-__device__ __forceinline__ ScoreLse score_lse_merge(ScoreLse p, ScoreLse q) {
-    if (p.m != p.m || q.m != q.m) return ScoreLse{NAN, 0.0};
-    const double m = fmax(p.m, q.m);
-    if (!(m > -INFINITY) || !(m < INFINITY)) return ScoreLse{m, m == INFINITY ? 1.0 : 0.0};    // all -inf so far, or +inf (or NaN)
-    return ScoreLse{m, p.a * exp(p.m - m) + q.a * exp(q.m - m)};                                // exp(-inf - m) = 0
-}
-__device__ __forceinline__ double score_lse_value(ScoreLse p) { return (p.m > -INFINITY && p.m < INFINITY) ? p.m + log(p.a) : p.m; }
+// (ScoreLse, score_lse_merge and score_lse_value -- the log-sum-exp state -- are in common.h: aggpost.hip merges with them too)
 
 // one block per image
 __global__ __launch_bounds__(SR_THREADS) void score_reduce_kernel(const float* nll, const float* lw, const float* la, const float* mu,
