@@ -371,6 +371,25 @@ int sv_sample_bwd(int dtype, const void* dlatent, const float* ls, const float* 
                   int mode, float temperature, int B, int ldc, int K, int Lpad,
                   float* dmu, float* dls, float* dla, void* stream);
 
+/* Every group of a batched launch in ONE grid (added under ABI 8: new symbols and a new struct only).  The groups tile the rows
+ * of mu / ls ([rows][ldc]), la / csoft ([rows][K]), eps and latent: group i covers rows [row0, row0 + rows), row0 = the end of
+ * group i - 1 (0 for the first).  mode, lam / lam_dev as above; u ([rows][K], mode 0), label, label_mix ([rows], modes 1, 2) are
+ * the GROUP's own arrays, indexed by the row within the group.  Each row is computed by the code of sv_sample_fwd / sv_sample_bwd:
+ * the results equal one call per group, bit for bit.  The table is read on the host before the launch (not kept): capturable.
+ * sv_sample_bwd_groups reads mode, row0 and rows only.                                                                        */
+#define SV_MAX_SAMPLE_GROUPS 8
+typedef struct {
+    int32_t mode, row0, rows, reserved0;
+    const float* u; const int64_t* label; const int64_t* label_mix;
+    float lam; int32_t reserved1; const float* lam_dev;
+} sv_sample_group;
+int sv_sample_fwd_groups(int dtype, const float* mu, const float* ls, const float* la, const float* eps,
+                         const sv_sample_group* groups, int ngroups, float temperature, int ldc, int K, int Lpad, void* latent,
+                         float* csoft, void* stream);
+int sv_sample_bwd_groups(int dtype, const void* dlatent, const float* ls, const float* eps, const float* csoft,
+                         const sv_sample_group* groups, int ngroups, float temperature, int ldc, int K, int Lpad,
+                         float* dmu, float* dls, float* dla, void* stream);
+
 /* ---- inference: the decoder's input from a counter-based normal stream, and the decoder's output as an image (latent.hip).
  * Added under ABI 8: new symbols only, no struct or signature changed.  Both validate their arguments before any HIP call
  * (null pointers, non-positive sizes, Lpad < ldc + K, unknown mode / dtype: SV_E_ARG / SV_E_SHAPE, nothing launched), take a
@@ -564,6 +583,16 @@ int sv_topk_hits(const float* score, const int64_t* label, int B, int K, int k, 
 int sv_mix_lerp(const float* a, const int64_t* index, float lam, const float* lam_dev, int B, int64_t row,
                 int exp_space, float* out, void* stream);
 
+/* The input side of the single-launch step in one pass (added under ABI 8: a new symbol only): from image_l, image_u (fp32 NCHW
+ * [B][C][H][W]), two pairings (int64 [B], values in [0, B)) and two mixing coefficients (host value, or device scalar when lam_*_dev
+ * is not NULL), out = NHWC `dtype` [4B][H][W][Cpad], channels >= C zero, holding the groups in the step's launch order:
+ * image_l | image_u | sv_mix_lerp(image_l, perm_l, lam_l) | sv_mix_lerp(image_u, perm_u, lam_u) -- bit for bit what sv_mix_lerp x 2,
+ * a concatenation and sv_nchw_to_nhwc give.  sm_img / mx_img (fp32 NCHW [B][C][H][W], each may be NULL) receive the two mixed
+ * batches as sv_mix_lerp writes them.  No allocation, no synchronisation: capturable.                                          */
+int sv_mix_pack(int dtype, const float* image_l, const float* image_u, const int64_t* perm_l, const int64_t* perm_u, float lam_l,
+                const float* lam_l_dev, float lam_u, const float* lam_u_dev, int B, int C, int H, int W, int Cpad, void* out,
+                float* sm_img, float* mx_img, void* stream);
+
 /* random permutations from uniform keys (the device-side replacement of torch.randperm, mixup.py:20,34): perm[rank of
  * key i] = i within each of `batches` key vectors of length n (<= 16384); ties: the lower index first.                */
 int sv_rank_permutation(const float* keys, int n, int batches, int64_t* perm, void* stream);
@@ -625,6 +654,20 @@ int sv_shot_targets2(const float* mu_l, const float* ls_l, const float* mu_u, co
                      const int64_t* label_l, const int64_t* perm_l, const int64_t* perm_u, float lam_l, const float* lam_l_dev,
                      float lam_u, const float* lam_u_dev, int Bl, int Bu, int D, int K, float* sm_mu, float* sm_sigma, float* lab_mix,
                      float* mx_mu, float* mx_sigma, float* mx_alpha, void* stream);
+
+/* The same stage on the decoder's own output (added under ABI 8: a new symbol and a new struct only): the reconstruction logits
+ * are read where the last ConvTranspose left them, rec[i] = NHWC `dtype` [B][HW][ld_rec] (channels < C), and the reconstruction
+ * gradient is written as the decoder's backward reads it, d_rec[i] = NHWC `dtype` [B][HW][ld_drec], channels >= C zero.
+ * base.rec / base.d_rec are ignored; everything else is sv_shot_loss_step2's, and base.n_per_img = C * HW.  Every reduction visits
+ * the logits in the order of the fp32 NCHW tensor, and the gradient is the fp32 value of sv_shot_loss_step2 rounded to `dtype`
+ * once: terms, the latent gradients and d_rec equal sv_nhwc_to_nchw -> sv_shot_loss_step2 -> sv_nchw_to_nhwc bit for bit (in
+ * deterministic mode too).  At most 2^31 - 1 logits per group.                                                               */
+typedef struct {
+    sv_shot_loss_args2 base;
+    int32_t dtype, C, HW, ld_rec, ld_drec, reserved0;
+    const void* rec[2]; void* d_rec[2];
+} sv_shot_loss_args3;
+int sv_shot_loss_step3(const sv_shot_loss_args3* a, void* stream);
 
 /* ---- K18 optimal-match pairing (lib/utils/mixup.py:9-18,93-99): index[i] = argmin_{j!=rank0} ----
  * second-smallest entry of row i of the pairwise Gaussian-KL matrix.                               */

@@ -100,6 +100,20 @@ class SvShotLossArgs2(C.Structure):
                 ("d_rec", C.c_void_p * 2), ("d_mu", C.c_void_p * 4), ("d_ls", C.c_void_p * 4), ("d_la", C.c_void_p * 4)]
 
 
+class SvShotLossArgs3(C.Structure):
+    _fields_ = [("base", SvShotLossArgs2), ("dtype", C.c_int32), ("C", C.c_int32), ("HW", C.c_int32), ("ld_rec", C.c_int32),
+                ("ld_drec", C.c_int32), ("reserved0", C.c_int32), ("rec", C.c_void_p * 2), ("d_rec", C.c_void_p * 2)]
+
+
+MAX_SAMPLE_GROUPS = 8            # include/shotvae_hip.h: SV_MAX_SAMPLE_GROUPS
+
+
+class SvSampleGroup(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("row0", C.c_int32), ("rows", C.c_int32), ("reserved0", C.c_int32), ("u", C.c_void_p),
+                ("label", C.c_void_p), ("label_mix", C.c_void_p), ("lam", C.c_float), ("reserved1", C.c_int32),
+                ("lam_dev", C.c_void_p)]
+
+
 class SvBnBranch(C.Structure):
     _fields_ = [("g", C.c_void_p), ("bsums", C.c_void_p), ("gamma", C.c_void_p), ("dgamma", C.c_void_p),
                 ("dbeta", C.c_void_p), ("replicas", C.c_int32), ("sparse", C.c_int32)]
@@ -143,6 +157,8 @@ _PROTOS = {
     "sv_ce_bwd": [P, P, I, I, P, P, P],
     "sv_sample_fwd": [I, P, P, P, P, P, P, P, F, P, I, F, I, I, I, I, P, P, P],
     "sv_sample_bwd": [I, P, P, P, P, I, F, I, I, I, I, P, P, P, P],
+    "sv_sample_fwd_groups": [I, P, P, P, P, C.POINTER(SvSampleGroup), I, F, I, I, I, P, P, P],
+    "sv_sample_bwd_groups": [I, P, P, P, P, C.POINTER(SvSampleGroup), I, F, I, I, I, P, P, P, P],
     "sv_latent_draw": [I, P, P, P, F, I64, I, P, P, I, I, I, I, P, P, P],
     "sv_image_out": [I, P, I, I, I, I, I, I, P, P, P],
     "sv_latent_sweep": [I, P, P, P, I64, P, I, I, I, I, I, I64, I, P, P, P],
@@ -163,6 +179,7 @@ _PROTOS = {
     "sv_post_fwd": [P, P, P, P, I, I, P, P],
     "sv_post_bwd": [P, P, P, P, I, I, P, P, P, P],
     "sv_mix_lerp": [P, P, F, P, I, I64, I, P, P],
+    "sv_mix_pack": [I, P, P, P, P, F, P, F, P, I, I, I, I, I, P, P, P, P],
     "sv_optimal_match": [P, P, I, I, P, P],
     "sv_rank_permutation": [P, I, I, P, P],
     "sv_shot_targets": [P, P, P, P, P, P, P, P, F, P, F, P, I, I, I, P, P, P, P, P, P, P],
@@ -170,6 +187,7 @@ _PROTOS = {
     "sv_shot_scale": [P, P, P, P, P],
     "sv_shot_loss_step": [C.POINTER(SvShotLossArgs), P],
     "sv_shot_loss_step2": [C.POINTER(SvShotLossArgs2), P],
+    "sv_shot_loss_step3": [C.POINTER(SvShotLossArgs3), P],
     "sv_shot_targets2": [P, P, P, P, P, P, P, P, F, P, F, P, I, I, I, I, P, P, P, P, P, P, P],
     "sv_sgd": [P, P, P, I64, F, F, F, F, I, P],
     "sv_adam": [P, P, P, P, I64, F, F, F, F, F, P, F, P],

@@ -957,15 +957,33 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* logits, const 
     for (int k = lane; k < K; k += 64) d[k] = (expf(z[k] - lse) - (k == (int)y ? 1.f : 0.f)) * g;
 }
 
+// the Cpad channels of ONE pixel: chan(c) is the fp32 value of channel c < C, the rest are zero; fp32 -> T is rounded here, for
+// every kernel that writes an NHWC pixel from fp32 values (nchw_to_nhwc_kernel, mix_pack_kernel, the NHWC loss stage)
+template <typename T, typename F>
+__device__ __forceinline__ void nhwc_store_pixel(T* dst, int C, int Cpad, F chan) {
+    typedef typename V8<T>::type V;
+    if (Cpad % 8 == 0) {
+        for (int c0 = 0; c0 < Cpad; c0 += 8) {
+            V v;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (T)(c0 + j < C ? chan(c0 + j) : 0.f);
+            *reinterpret_cast<V*>(dst + c0) = v;
+        }
+    } else {
+        for (int c = 0; c < Cpad; ++c) dst[c] = (T)(c < C ? chan(c) : 0.f);
+    }
+}
+
 // ---------------------------------------------------------------------------------------- sampler
+// row b of one sampler group (every pointer is the group's own: its row 0); the block = 128 threads
 template <typename T>
-__global__ __launch_bounds__(128) void sample_fwd_kernel(const float* mu, const float* ls, const float* la,
-                                                         const float* eps, const float* u,
-                                                         const int64_t* label, const int64_t* label_mix,
-                                                         float lam, const float* lam_dev, int mode,
-                                                         float temperature, int B,
-                                                         int ldc, int K, int Lpad, T* latent, float* csoft) {
-    const int b = blockIdx.x, tid = threadIdx.x;
+__device__ __forceinline__ void sample_fwd_row(const float* mu, const float* ls, const float* la,
+                                               const float* eps, const float* u,
+                                               const int64_t* label, const int64_t* label_mix,
+                                               float lam, const float* lam_dev, int mode,
+                                               float temperature, int b,
+                                               int ldc, int K, int Lpad, T* latent, float* csoft) {
+    const int tid = threadIdx.x;
     if (lam_dev) lam = lam_dev[0];
     __shared__ float red[2];
     __shared__ float bc[2];
@@ -1016,11 +1034,40 @@ __global__ __launch_bounds__(128) void sample_fwd_kernel(const float* mu, const 
 }
 
 template <typename T>
-__global__ __launch_bounds__(128) void sample_bwd_kernel(const T* dlatent, const float* ls, const float* eps,
-                                                         const float* csoft, int mode, float temperature,
-                                                         int B, int ldc, int K, int Lpad, float* dmu,
-                                                         float* dls, float* dla) {
-    const int b = blockIdx.x, tid = threadIdx.x;
+__global__ __launch_bounds__(128) void sample_fwd_kernel(const float* mu, const float* ls, const float* la,
+                                                         const float* eps, const float* u,
+                                                         const int64_t* label, const int64_t* label_mix,
+                                                         float lam, const float* lam_dev, int mode,
+                                                         float temperature, int B,
+                                                         int ldc, int K, int Lpad, T* latent, float* csoft) {
+    sample_fwd_row<T>(mu, ls, la, eps, u, label, label_mix, lam, lam_dev, mode, temperature, blockIdx.x, ldc, K, Lpad, latent, csoft);
+}
+
+// every group of a batched launch in ONE grid: block = one row of the launch, the table says which group's arguments it runs with
+struct sample_groups { sv_sample_group g[SV_MAX_SAMPLE_GROUPS]; int n; };
+__device__ __forceinline__ sv_sample_group sample_group_of(const sample_groups& t, int row) {
+    sv_sample_group g = t.g[0];                  // (constant indices only: the table stays in the kernel's argument segment)
+#pragma unroll
+    for (int i = 1; i < SV_MAX_SAMPLE_GROUPS; ++i)
+        if (i < t.n && row >= t.g[i].row0) g = t.g[i];                    // (row0 ascending: checked by the entry points)
+    return g;
+}
+template <typename T>
+__global__ __launch_bounds__(128) void sample_fwd_groups_kernel(const float* mu, const float* ls, const float* la, const float* eps,
+                                                                const sample_groups t, float temperature, int ldc, int K, int Lpad,
+                                                                T* latent, float* csoft) {
+    const sv_sample_group g = sample_group_of(t, blockIdx.x);
+    const int64_t r0 = g.row0;
+    sample_fwd_row<T>(mu + r0 * ldc, ls + r0 * ldc, la + r0 * K, eps + r0 * ldc, g.u, g.label, g.label_mix, g.lam, g.lam_dev, g.mode,
+                      temperature, (int)(blockIdx.x - r0), ldc, K, Lpad, latent + r0 * Lpad, csoft + r0 * K);
+}
+
+template <typename T>
+__device__ __forceinline__ void sample_bwd_row(const T* dlatent, const float* ls, const float* eps,
+                                               const float* csoft, int mode, float temperature,
+                                               int b, int ldc, int K, int Lpad, float* dmu,
+                                               float* dls, float* dla) {
+    const int tid = threadIdx.x;
     __shared__ float bc[2];
     const T* d = dlatent + (int64_t)b * Lpad;
     for (int j = tid; j < ldc; j += 128) {
@@ -1042,11 +1089,58 @@ __global__ __launch_bounds__(128) void sample_bwd_kernel(const T* dlatent, const
         }
     }
 }
+template <typename T>
+__global__ __launch_bounds__(128) void sample_bwd_kernel(const T* dlatent, const float* ls, const float* eps,
+                                                         const float* csoft, int mode, float temperature,
+                                                         int B, int ldc, int K, int Lpad, float* dmu,
+                                                         float* dls, float* dla) {
+    sample_bwd_row<T>(dlatent, ls, eps, csoft, mode, temperature, blockIdx.x, ldc, K, Lpad, dmu, dls, dla);
+}
+template <typename T>
+__global__ __launch_bounds__(128) void sample_bwd_groups_kernel(const T* dlatent, const float* ls, const float* eps, const float* csoft,
+                                                                const sample_groups t, float temperature, int ldc, int K, int Lpad,
+                                                                float* dmu, float* dls, float* dla) {
+    const sv_sample_group g = sample_group_of(t, blockIdx.x);
+    const int64_t r0 = g.row0;
+    sample_bwd_row<T>(dlatent + r0 * Lpad, ls + r0 * ldc, eps + r0 * ldc, csoft + r0 * K, g.mode, temperature, (int)(blockIdx.x - r0),
+                      ldc, K, Lpad, dmu + r0 * ldc, dls + r0 * ldc, dla + r0 * K);
+}
 
 // ---------------------------------------------------------------------------------------- losses
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
-__device__ __forceinline__ void elbo_fwd_dev(const float* x, const float* xr, int64_t n_img,
+// Where a loss kernel finds the reconstruction logits.  Every reduction runs over the LOGICAL fp32 NCHW tensor [B][C][HW] -- element
+// i, four consecutive ones per vector -- whether it is stored as that tensor (rec_nchw) or is still the decoder's NHWC output
+// [B][HW][ld] of T (rec_nhwc: bf16 -> fp32 is exact, so the values and the order of every sum are those of the converted tensor).
+struct rec_nchw {
+    const float* p;
+    __device__ __forceinline__ float at(int64_t i) const { return p[i]; }
+    __device__ __forceinline__ f32x4 at4(int64_t i4) const { return reinterpret_cast<const f32x4*>(p)[i4]; }
+};
+template <typename T>
+struct rec_nhwc {
+    const T* p; unsigned C, HW, ld;              // (B * C * HW < 2^31: checked by the entry point)
+    __device__ __forceinline__ float at(int64_t i) const {
+        const unsigned e = (unsigned)i, bc = e / HW, px = e - bc * HW, b = bc / C, c = bc - b * C;
+        return to_f(p[((size_t)b * HW + px) * ld + c]);
+    }
+    __device__ __forceinline__ f32x4 at4(int64_t i4) const {
+        const unsigned e = 4u * (unsigned)i4, bc = e / HW, px = e - bc * HW, b = bc / C, c = bc - b * C;
+        f32x4 r;
+        if (px + 3 < HW) {                       // the four share a channel plane: consecutive pixels
+            const T* q = p + ((size_t)b * HW + px) * ld + c;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = to_f(q[(size_t)j * ld]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = at((int64_t)e + j);
+        }
+        return r;
+    }
+};
+
+template <typename R>
+__device__ __forceinline__ void elbo_fwd_dev(const float* x, const R xr, int64_t n_img,
                                                        const float* mu, const float* ls, const float* la,
                                                        int B, int ldc, int K, int bce, float x_sigma,
                                                        float log_prior, float* out3, int ostride) {
@@ -1057,9 +1151,8 @@ __device__ __forceinline__ void elbo_fwd_dev(const float* x, const float* xr, in
     float s = 0.f;
     const int64_t n4 = n_img / 4;
     const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
-    const f32x4* r4 = reinterpret_cast<const f32x4*>(xr);
     for (int64_t i = t0; i < n4; i += stride) {
-        const f32x4 a = x4[i], r = r4[i];
+        const f32x4 a = x4[i], r = xr.at4(i);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (bce) s += fmaxf(r[j], 0.f) - r[j] * a[j] + log1pf(expf(-fabsf(r[j])));
@@ -1067,7 +1160,7 @@ __device__ __forceinline__ void elbo_fwd_dev(const float* x, const float* xr, in
         }
     }
     for (int64_t i = n4 * 4 + t0; i < n_img; i += stride) {
-        const float a = x[i], r = xr[i];
+        const float a = x[i], r = xr.at(i);
         if (bce) s += fmaxf(r, 0.f) - r * a + log1pf(expf(-fabsf(r)));
         else { const float d = sigmoidf_(r) - a; s += d * d; }
     }
@@ -1088,25 +1181,52 @@ __device__ __forceinline__ void elbo_fwd_dev(const float* x, const float* xr, in
     kd = block_sum(kd, red);
     if (threadIdx.x == 0 && kd != 0.f) atomicAdd(out3 + 2, kd / (float)B);
 }
-__global__ __launch_bounds__(256) void elbo_fwd_kernel(const float* x, const float* xr, int64_t n_img,
+template <typename R>
+__global__ __launch_bounds__(256) void elbo_fwd_kernel(const float* x, const R xr, int64_t n_img,
                                                        const float* mu, const float* ls, const float* la,
                                                        int B, int ldc, int K, int bce, float x_sigma,
                                                        float log_prior, float* out3, int ostride) { elbo_fwd_dev(x, xr, n_img, mu, ls, la, B, ldc, K, bce, x_sigma, log_prior, out3, ostride); }
 
-__device__ __forceinline__ void elbo_bwd_dev(const float* x, const float* xr, int64_t n_img,
+// gradient of the reconstruction term w.r.t. ONE logit r (image value x); rs = the upstream gradient times the term's scale
+__device__ __forceinline__ float elbo_bwd_rec_val(float x, float r, float rs, int bce) {
+    const float sg = sigmoidf_(r);
+    const float d = sg - x;
+    return bce ? rs * d : rs * d * sg * (1.f - sg);
+}
+// the reconstruction gradient of elbo_bwd_dev, by storage: fp32 NCHW logits and gradient, element by element ...
+struct rec_grad_nchw {
+    const float* xr; float* dxr;
+    __device__ __forceinline__ void run(const float* x, int64_t n_img, float rs, int bce, int64_t t0, int64_t stride) const {
+        for (int64_t i = t0; i < n_img; i += stride) dxr[i] = elbo_bwd_rec_val(x[i], xr[i], rs, bce);
+    }
+};
+// ... or the decoder's NHWC logits [B][HW][ldr] and the NHWC gradient [B][HW][ldd] its backward reads (padding channels zero), pixel
+// by pixel: the same fp32 value per element, rounded to T as the NCHW -> NHWC conversion of the fp32 gradient rounds it
+template <typename T>
+struct rec_grad_nhwc {
+    const T* xr; T* dxr; int C, HW, ldr, ldd;
+    __device__ __forceinline__ void run(const float* x, int64_t n_img, float rs, int bce, int64_t t0, int64_t stride) const {
+        const int64_t npix = n_img / C;
+        for (int64_t q = t0; q < npix; q += stride) {
+            const int64_t b = q / HW, px = q - b * HW;
+            const float* xi = x + b * C * HW + px;
+            const T* r = xr + q * ldr;
+            nhwc_store_pixel(dxr + q * ldd, C, ldd, [&](int c) { return elbo_bwd_rec_val(xi[(int64_t)c * HW], to_f(r[c]), rs, bce); });
+        }
+    }
+};
+
+template <typename RG>
+__device__ __forceinline__ void elbo_bwd_dev(const float* x, const RG rg, int64_t n_img,
                                                        const float* mu, const float* ls, const float* la,
                                                        int B, int ldc, int K, int bce, float x_sigma,
-                                                       float log_prior, const float* gout3, float* dxr,
+                                                       float log_prior, const float* gout3,
                                                        float* dmu, float* dls, float* dla) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const float g0 = gout3[0], g1 = gout3[1], g2 = gout3[2];
     const float rs = g0 * (bce ? 1.f / (float)B : 1.f / ((float)B * x_sigma * x_sigma));
-    for (int64_t i = t0; i < n_img; i += stride) {
-        const float sg = sigmoidf_(xr[i]);
-        const float d = sg - x[i];
-        dxr[i] = bce ? rs * d : rs * d * sg * (1.f - sg);
-    }
+    rg.run(x, n_img, rs, bce, t0, stride);
     const float c1 = g1 / (float)B, c2 = g2 / (float)B;
     for (int64_t i = t0; i < (int64_t)B * ldc; i += stride) {
         dmu[i] = c1 * mu[i];
@@ -1117,11 +1237,12 @@ __device__ __forceinline__ void elbo_bwd_dev(const float* x, const float* xr, in
         dla[i] = c2 * expf(l) * (l - log_prior + 1.f);
     }
 }
-__global__ __launch_bounds__(256) void elbo_bwd_kernel(const float* x, const float* xr, int64_t n_img,
+template <typename RG>
+__global__ __launch_bounds__(256) void elbo_bwd_kernel(const float* x, const RG rg, int64_t n_img,
                                                        const float* mu, const float* ls, const float* la,
                                                        int B, int ldc, int K, int bce, float x_sigma,
-                                                       float log_prior, const float* gout3, float* dxr,
-                                                       float* dmu, float* dls, float* dla) { elbo_bwd_dev(x, xr, n_img, mu, ls, la, B, ldc, K, bce, x_sigma, log_prior, gout3, dxr, dmu, dls, dla); }
+                                                       float log_prior, const float* gout3,
+                                                       float* dmu, float* dls, float* dla) { elbo_bwd_dev(x, rg, n_img, mu, ls, la, B, ldc, K, bce, x_sigma, log_prior, gout3, dmu, dls, dla); }
 
 __device__ __forceinline__ void cls_fwd_dev(const float* pred, const float* label, const float* w,
                                                       int B, int K, float* out, int ostride) {
@@ -1190,26 +1311,46 @@ __global__ __launch_bounds__(256) void post_bwd_kernel(const float* mu, const fl
 
 // ---- the loss stage of a step in three launches (sv_shot_loss_step2): at ~5 us per launch the 12 reduction / gradient kernels
 //      of the stage cost more in launches than in work.  blockIdx.y selects the part; every part is the kernel above, unchanged.
-struct shot_elbo_part { const float* x; const float* xr; const float* mu; const float* ls; const float* la; int B; float* out3;
-                        const float* gout3; float* dxr; float* dmu; float* dls; float* dla; };
+// (xr / dxr: fp32 NCHW for sv_shot_loss_step2; the decoder's NHWC logits and the NHWC gradient of `T` for sv_shot_loss_step3)
+struct shot_elbo_part { const float* x; const void* xr; const float* mu; const float* ls; const float* la; int B; float* out3;
+                        const float* gout3; void* dxr; float* dmu; float* dls; float* dla; };
 struct shot_post_part { const float* la; const float* label; const float* mu; const float* ls; const float* mt; const float* st; int B;
                         float* out_cls; float* out_post; const float* g_cls; const float* g_post; float* dla; float* dmu; float* dls; };
-struct shot_parts { shot_elbo_part e[2]; shot_post_part q[2]; int64_t n_per_img; int D, K, bce; float x_sigma, log_prior; };
+struct shot_parts { shot_elbo_part e[2]; shot_post_part q[2]; int64_t n_per_img; int D, K, bce; float x_sigma, log_prior;
+                    int C, HW, ldr, ldd; };            // (the NHWC form only)
+// the accessors of a part: NHWC = false -> the fp32 NCHW tensors, true -> NHWC of T
+template <bool NHWC, typename T> struct shot_rec;
+template <typename T> struct shot_rec<false, T> {
+    typedef rec_nchw R;  typedef rec_grad_nchw RG;
+    static __host__ __device__ __forceinline__ R fwd(const shot_parts&, const shot_elbo_part& e) { return R{(const float*)e.xr}; }
+    static __host__ __device__ __forceinline__ RG bwd(const shot_parts&, const shot_elbo_part& e) { return RG{(const float*)e.xr, (float*)e.dxr}; }
+};
+template <typename T> struct shot_rec<true, T> {
+    typedef rec_nhwc<T> R;  typedef rec_grad_nhwc<T> RG;
+    static __host__ __device__ __forceinline__ R fwd(const shot_parts& P, const shot_elbo_part& e) {
+        return R{(const T*)e.xr, (unsigned)P.C, (unsigned)P.HW, (unsigned)P.ldr};
+    }
+    static __host__ __device__ __forceinline__ RG bwd(const shot_parts& P, const shot_elbo_part& e) {
+        return RG{(const T*)e.xr, (T*)e.dxr, P.C, P.HW, P.ldr, P.ldd};
+    }
+};
 
+template <bool NHWC, typename T>
 __global__ __launch_bounds__(256) void shot_elbo_fwd2_kernel(const shot_parts P) {
     const shot_elbo_part& e = P.e[blockIdx.y];
-    elbo_fwd_dev(e.x, e.xr, P.n_per_img * e.B, e.mu, e.ls, e.la, e.B, P.D, P.K, P.bce, P.x_sigma, P.log_prior, e.out3, 0);
+    elbo_fwd_dev(e.x, shot_rec<NHWC, T>::fwd(P, e), P.n_per_img * e.B, e.mu, e.ls, e.la, e.B, P.D, P.K, P.bce, P.x_sigma, P.log_prior, e.out3, 0);
 }
 __global__ __launch_bounds__(256) void shot_post_fwd4_kernel(const shot_parts P) {
     const shot_post_part& q = P.q[blockIdx.y >> 1];
     if (blockIdx.y & 1) post_fwd_dev(q.mu, q.ls, q.mt, q.st, q.B, P.D, q.out_post, 0);
     else cls_fwd_dev(q.la, q.label, nullptr, q.B, P.K, q.out_cls, 0);
 }
+template <bool NHWC, typename T>
 __global__ __launch_bounds__(256) void shot_bwd6_kernel(const shot_parts P) {
     const int y = blockIdx.y;
     if (y < 2) {
         const shot_elbo_part& e = P.e[y];
-        elbo_bwd_dev(e.x, e.xr, P.n_per_img * e.B, e.mu, e.ls, e.la, e.B, P.D, P.K, P.bce, P.x_sigma, P.log_prior, e.gout3, e.dxr, e.dmu, e.dls, e.dla);
+        elbo_bwd_dev(e.x, shot_rec<NHWC, T>::bwd(P, e), P.n_per_img * e.B, e.mu, e.ls, e.la, e.B, P.D, P.K, P.bce, P.x_sigma, P.log_prior, e.gout3, e.dmu, e.dls, e.dla);
     } else {
         const shot_post_part& q = P.q[(y - 2) >> 1];
         if (y & 1) post_bwd_dev(q.mu, q.ls, q.mt, q.st, q.B, P.D, q.g_post, q.dmu, q.dls);
@@ -1306,6 +1447,10 @@ __global__ void shot_scale_kernel(const float* coef, const float* g_sup, const f
 }
 
 // ---------------------------------------------------------------------------------------- mixup
+// lam * p + (1 - lam) * q with the rounding points spelled out -- (1 - lam) * q rounded, then ONE fused multiply-add -- so that every
+// kernel that mixes (mix_lerp_kernel, mix_pack_kernel in both dtypes) gives the same bits whatever the compiler would contract
+__device__ __forceinline__ float mix_lerp_val(float p, float q, float lam) { return __builtin_fmaf(lam, p, (1.f - lam) * q); }
+
 __global__ void mix_lerp_kernel(const float* a, const int64_t* index, float lam, const float* lam_dev, int B,
                                 int64_t row, int exp_space, float* out) {
     if (lam_dev) lam = lam_dev[0];
@@ -1315,7 +1460,7 @@ __global__ void mix_lerp_kernel(const float* a, const int64_t* index, float lam,
     const int64_t src = index[b];
     float p = a[(int64_t)b * row + j], q = a[src * row + j];
     if (exp_space) { p = expf(p); q = expf(q); }
-    out[(int64_t)b * row + j] = lam * p + (1.f - lam) * q;
+    out[(int64_t)b * row + j] = mix_lerp_val(p, q, lam);
 }
 
 // pairwise Gaussian KL(N_i || N_j), second-smallest per row (torch.topk(k=2, largest=False)[:,1])
@@ -1767,24 +1912,46 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* p, const float* g, floa
 // ---------------------------------------------------------------------------------------- layout
 // one thread per pixel: C strided channel reads (coalesced across the pixels of a wave), the Cpad outputs of the pixel
 // as 16-byte stores (one 2-byte store per thread ran at 1.5 TB/s)
+// (nhwc_store_pixel, above the sampler: the pixel store every fp32 -> NHWC writer shares)
 template <typename T>
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* in, int B, int C, int HW, int Cpad, T* out) {
-    typedef typename V8<T>::type V;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;     // over B*HW
     if (i >= (int64_t)B * HW) return;
     const int64_t b = i / HW, p = i - b * HW;
     const float* src = in + b * C * HW + p;
-    T* dst = out + i * Cpad;
-    if (Cpad % 8 == 0) {
-        for (int c0 = 0; c0 < Cpad; c0 += 8) {
-            V v;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = (T)(c0 + j < C ? src[(int64_t)(c0 + j) * HW] : 0.f);
-            *reinterpret_cast<V*>(dst + c0) = v;
-        }
-    } else {
-        for (int c = 0; c < Cpad; ++c) dst[c] = (T)(c < C ? src[(int64_t)c * HW] : 0.f);
-    }
+    nhwc_store_pixel(out + i * Cpad, C, Cpad, [&](int c) { return src[(int64_t)c * HW]; });
+}
+
+// The input side of the single-launch step in one pass: out [4B][HW][Cpad] = the groups (1) image_l, (3) image_u, (2) the smoothed
+// labelled batch lerp(image_l, perm_l, lam_l), (4) the mixed unlabelled batch lerp(image_u, perm_u, lam_u) -- what sv_mix_lerp x 2,
+// a concatenation and sv_nchw_to_nhwc produce.  One thread per source pixel: it writes the pixel itself and its mixed twin (the
+// fp32 mix is mix_lerp_kernel's, rounded to T once, as the conversion of the stored fp32 batch was); sm_img / mx_img (fp32 NCHW,
+// optional) receive the mixed batches for a caller that returns them.
+template <typename T>
+__global__ __launch_bounds__(256) void mix_pack_kernel(const float* image_l, const float* image_u, const int64_t* perm_l,
+                                                       const int64_t* perm_u, float lam_l, const float* lam_l_dev, float lam_u,
+                                                       const float* lam_u_dev, int B, int C, int HW, int Cpad, T* out,
+                                                       float* sm_img, float* mx_img) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;     // over 2*B*HW: the labelled pixels, then the unlabelled
+    const int64_t half = (int64_t)B * HW;
+    if (i >= 2 * half) return;
+    const int s = i >= half ? 1 : 0;
+    const int64_t r = i - s * half;
+    const int64_t b = r / HW, p = r - b * HW;
+    const float* img = s ? image_u : image_l;
+    float lam = s ? lam_u : lam_l;
+    const float* lam_dev = s ? lam_u_dev : lam_l_dev;
+    if (lam_dev) lam = lam_dev[0];
+    const int64_t pb = (s ? perm_u : perm_l)[b];
+    const float* own = img + b * C * HW + p;
+    const float* other = img + pb * C * HW + p;
+    float* keep = s ? mx_img : sm_img;
+    nhwc_store_pixel(out + i * Cpad, C, Cpad, [&](int c) { return own[(int64_t)c * HW]; });
+    nhwc_store_pixel(out + (2 * half + i) * Cpad, C, Cpad, [&](int c) {
+        const float m = mix_lerp_val(own[(int64_t)c * HW], other[(int64_t)c * HW], lam);
+        if (keep) keep[b * C * HW + (int64_t)c * HW + p] = m;
+        return m;
+    });
 }
 template <typename T>
 __global__ void nhwc_to_nchw_kernel(const T* in, int B, int C, int HW, int ld, float* out) {
@@ -2355,26 +2522,94 @@ int sv_sample_bwd(int dtype, const void* dlatent, const float* ls, const float* 
     return sv_check_launch("sv_sample_bwd");
 }
 
+// the table of a grouped sampler launch, checked and copied; *rows = the rows of the launch (the groups tile [0, rows))
+static int sample_table(const sv_sample_group* groups, int ngroups, bool fwd, const char* who, sample_groups* t, int* rows) {
+    SV_REQUIRE(groups && ngroups >= 1 && ngroups <= SV_MAX_SAMPLE_GROUPS, SV_E_ARG, "%s: 1 to %d groups", who, SV_MAX_SAMPLE_GROUPS);
+    int next = 0;
+    for (int i = 0; i < ngroups; ++i) {
+        const sv_sample_group& g = groups[i];
+        SV_REQUIRE(g.row0 == next && g.rows > 0, SV_E_ARG, "%s: group %d covers rows %d + %d, expected to start at %d", who, i, g.row0,
+                   g.rows, next);
+        SV_REQUIRE(g.mode >= 0 && g.mode <= 2, SV_E_ARG, "%s: group %d: mode %d", who, i, g.mode);
+        if (fwd)
+            SV_REQUIRE((g.mode == 0 && g.u) || (g.mode == 1 && g.label) || (g.mode == 2 && g.label && g.label_mix), SV_E_ARG,
+                       "%s: group %d: mode %d inputs missing", who, i, g.mode);
+        t->g[i] = g;
+        next += g.rows;
+    }
+    for (int i = ngroups; i < SV_MAX_SAMPLE_GROUPS; ++i) t->g[i] = sv_sample_group{};
+    t->n = ngroups;
+    *rows = next;
+    return SV_OK;
+}
+
+int sv_sample_fwd_groups(int dtype, const float* mu, const float* ls, const float* la, const float* eps, const sv_sample_group* groups,
+                         int ngroups, float temperature, int ldc, int K, int Lpad, void* latent, float* csoft, void* stream) {
+    SvProfScope prof_scope(stream);
+    SV_REQUIRE(mu && ls && la && eps && latent && csoft, SV_E_ARG, "sv_sample_fwd_groups: null");
+    SV_REQUIRE(ldc > 0 && K > 0 && Lpad >= ldc + K, SV_E_SHAPE, "sv_sample_fwd_groups: Lpad");
+    sample_groups t;
+    int rows = 0;
+    const int rc = sample_table(groups, ngroups, true, "sv_sample_fwd_groups", &t, &rows);
+    if (rc != SV_OK) return rc;
+    DISPATCH_T(dtype, hipLaunchKernelGGL((sample_fwd_groups_kernel<T>), dim3(rows), dim3(128), 0, (hipStream_t)stream, mu, ls, la, eps, t,
+                                         temperature, ldc, K, Lpad, (T*)latent, csoft));
+    return sv_check_launch("sv_sample_fwd_groups");
+}
+
+int sv_sample_bwd_groups(int dtype, const void* dlatent, const float* ls, const float* eps, const float* csoft,
+                         const sv_sample_group* groups, int ngroups, float temperature, int ldc, int K, int Lpad, float* dmu, float* dls,
+                         float* dla, void* stream) {
+    SvProfScope prof_scope(stream);
+    SV_REQUIRE(dlatent && ls && eps && csoft && dmu && dls && dla, SV_E_ARG, "sv_sample_bwd_groups: null");
+    SV_REQUIRE(ldc > 0 && K > 0 && Lpad >= ldc + K, SV_E_SHAPE, "sv_sample_bwd_groups: Lpad");
+    sample_groups t;
+    int rows = 0;
+    const int rc = sample_table(groups, ngroups, false, "sv_sample_bwd_groups", &t, &rows);
+    if (rc != SV_OK) return rc;
+    DISPATCH_T(dtype, hipLaunchKernelGGL((sample_bwd_groups_kernel<T>), dim3(rows), dim3(128), 0, (hipStream_t)stream, (const T*)dlatent,
+                                         ls, eps, csoft, t, temperature, ldc, K, Lpad, dmu, dls, dla));
+    return sv_check_launch("sv_sample_bwd_groups");
+}
+
 static float log_prior_f32(int K) {
     // the reference builds log(float32(1/K)) in float32 (lib/criterion.py:29-30)
     const float p = (float)(1.0 / (double)K);
     return logf(p);
 }
 
-int sv_elbo_fwd(const float* x, const float* x_rec, int64_t n_per_img, const float* mu, const float* ls,
-                const float* la, int B, int ldc, int K, int bce, float x_sigma, float* out3, void* stream) {
-    SvProfScope prof_scope(stream);
-    SV_REQUIRE(x && x_rec && mu && ls && la && out3, SV_E_ARG, "sv_elbo_fwd: null");
+// sv_elbo_fwd / sv_elbo_bwd for either storage of the reconstruction (R / RG: the accessors of the loss section)
+extern "C++" {
+template <typename R>
+static int elbo_fwd_launch(const float* x, const R x_rec, int64_t n_per_img, const float* mu, const float* ls,
+                           const float* la, int B, int ldc, int K, int bce, float x_sigma, float* out3, void* stream) {
     const int64_t n = n_per_img * B;
     // (three float atomics per block on the same three addresses: 256 blocks, not 1 024 -- the tail of serialised atomics
     //  was most of this kernel's 26 us)
     const int P = nblocks(n / 4, 1024, 256);
     float* w = nullptr;
     if (sv_deterministic() && P > 1 && !(w = det_slots(P, 3, 1, (hipStream_t)stream))) return SV_E_HIP;
-    hipLaunchKernelGGL(elbo_fwd_kernel, dim3(P), dim3(256), 0, (hipStream_t)stream, x, x_rec,
+    hipLaunchKernelGGL((elbo_fwd_kernel<R>), dim3(P), dim3(256), 0, (hipStream_t)stream, x, x_rec,
                        n, mu, ls, la, B, ldc, K, bce, x_sigma, log_prior_f32(K), w ? w : out3, w ? 3 : 0);
     if (w) det_collect(w, P, 3, 1, out3, (hipStream_t)stream);
     return sv_check_launch("sv_elbo_fwd");
+}
+template <typename RG>
+static int elbo_bwd_launch(const float* x, const RG rg, int64_t n_per_img, const float* mu, const float* ls,
+                           const float* la, int B, int ldc, int K, int bce, float x_sigma, const float* gout3,
+                           float* dmu, float* dls, float* dla, void* stream) {
+    const int64_t n = n_per_img * B;
+    hipLaunchKernelGGL((elbo_bwd_kernel<RG>), dim3(nblocks(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, x, rg, n,
+                       mu, ls, la, B, ldc, K, bce, x_sigma, log_prior_f32(K), gout3, dmu, dls, dla);
+    return sv_check_launch("sv_elbo_bwd");
+}
+}  // extern "C++"
+
+int sv_elbo_fwd(const float* x, const float* x_rec, int64_t n_per_img, const float* mu, const float* ls,
+                const float* la, int B, int ldc, int K, int bce, float x_sigma, float* out3, void* stream) {
+    SvProfScope prof_scope(stream);
+    SV_REQUIRE(x && x_rec && mu && ls && la && out3, SV_E_ARG, "sv_elbo_fwd: null");
+    return elbo_fwd_launch(x, rec_nchw{x_rec}, n_per_img, mu, ls, la, B, ldc, K, bce, x_sigma, out3, stream);
 }
 
 int sv_elbo_bwd(const float* x, const float* x_rec, int64_t n_per_img, const float* mu, const float* ls,
@@ -2382,10 +2617,7 @@ int sv_elbo_bwd(const float* x, const float* x_rec, int64_t n_per_img, const flo
                 float* dmu, float* dls, float* dla, void* stream) {
     SvProfScope prof_scope(stream);
     SV_REQUIRE(x && x_rec && mu && ls && la && gout3 && dx_rec && dmu && dls && dla, SV_E_ARG, "sv_elbo_bwd: null");
-    const int64_t n = n_per_img * B;
-    hipLaunchKernelGGL(elbo_bwd_kernel, dim3(nblocks(n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, x, x_rec, n,
-                       mu, ls, la, B, ldc, K, bce, x_sigma, log_prior_f32(K), gout3, dx_rec, dmu, dls, dla);
-    return sv_check_launch("sv_elbo_bwd");
+    return elbo_bwd_launch(x, rec_grad_nchw{x_rec, dx_rec}, n_per_img, mu, ls, la, B, ldc, K, bce, x_sigma, gout3, dmu, dls, dla, stream);
 }
 
 int sv_cls_fwd(const float* predict, const float* label, const float* weight, int B, int K, float* out, void* stream) {
@@ -2494,12 +2726,14 @@ int sv_shot_loss_step(const sv_shot_loss_args* a, void* stream) {
     return sv_shot_loss_step2(&b, stream);
 }
 
-int sv_shot_loss_step2(const sv_shot_loss_args2* a, void* stream) {
-    SV_REQUIRE(a && a->image_l && a->image_u && a->label_l && a->perm_l && a->perm_u && a->terms && a->coef && a->tgt && a->Bl > 0 &&
-               a->Bu > 0 && a->D > 0 && a->K > 0, SV_E_ARG, "sv_shot_loss_step2: bad argument");
-    for (int g = 0; g < 4; ++g)
-        SV_REQUIRE(a->mu[g] && a->ls[g] && a->la[g] && a->d_mu[g] && a->d_ls[g] && a->d_la[g], SV_E_ARG, "sv_shot_loss_step2: group %d: null", g);
-    SV_REQUIRE(a->rec[0] && a->rec[1] && a->d_rec[0] && a->d_rec[1], SV_E_ARG, "sv_shot_loss_step2: reconstruction: null");
+// where the stage finds the reconstructions and puts their gradients: sv_shot_loss_step2's fp32 NCHW pairs, or (sv_shot_loss_step3)
+// the decoder's NHWC logits and the NHWC gradient of T
+struct shot_rec_io { const void* rec[2]; void* d_rec[2]; int C, HW, ldr, ldd; };
+
+// the stage itself (`a`: everything but the reconstruction pointers, which come from `io`)
+extern "C++" {
+template <bool NHWC, typename T>
+static int shot_loss_step_impl(const sv_shot_loss_args2* a, const shot_rec_io& io, void* stream) {
     const int Bl = a->Bl, Bu = a->Bu, D = a->D, K = a->K;
     const int64_t n = a->n_per_img;
     // targets: sm_mu | sm_sigma [Bl][D], mx_mu | mx_sigma [Bu][D], lab_mix [Bl][K], mx_alpha [Bu][K]
@@ -2516,12 +2750,13 @@ int sv_shot_loss_step2(const sv_shot_loss_args2* a, void* stream) {
         SvProfScope prof_scope(stream);
         shot_parts P;
         P.n_per_img = n; P.D = D; P.K = K; P.bce = a->bce; P.x_sigma = a->x_sigma; P.log_prior = log_prior_f32(K);
+        P.C = io.C; P.HW = io.HW; P.ldr = io.ldr; P.ldd = io.ldd;
         const float* img[2] = {a->image_l, a->image_u};
         const int Bs[2] = {Bl, Bu};
         for (int i = 0; i < 2; ++i) {
             shot_elbo_part& e = P.e[i];
-            e.x = img[i]; e.xr = a->rec[i]; e.mu = a->mu[i]; e.ls = a->ls[i]; e.la = a->la[i]; e.B = Bs[i]; e.out3 = a->terms + 3 * i;
-            e.gout3 = a->coef + 3 * i; e.dxr = a->d_rec[i]; e.dmu = a->d_mu[i]; e.dls = a->d_ls[i]; e.dla = a->d_la[i];
+            e.x = img[i]; e.xr = io.rec[i]; e.mu = a->mu[i]; e.ls = a->ls[i]; e.la = a->la[i]; e.B = Bs[i]; e.out3 = a->terms + 3 * i;
+            e.gout3 = a->coef + 3 * i; e.dxr = io.d_rec[i]; e.dmu = a->d_mu[i]; e.dls = a->d_ls[i]; e.dla = a->d_la[i];
             shot_post_part& q = P.q[i];
             q.la = a->la[2 + i]; q.label = i ? mx_alpha : lab_mix; q.mu = a->mu[2 + i]; q.ls = a->ls[2 + i];
             q.mt = i ? mx_mu : sm_mu; q.st = i ? mx_sigma : sm_sigma; q.B = Bs[i];
@@ -2530,7 +2765,7 @@ int sv_shot_loss_step2(const sv_shot_loss_args2* a, void* stream) {
         }
         const int Bmax = Bl > Bu ? Bl : Bu;
         hipStream_t s_ = (hipStream_t)stream;
-        hipLaunchKernelGGL(shot_elbo_fwd2_kernel, dim3(nblocks(n * Bmax / 4, 1024, 256), 2), dim3(256), 0, s_, P);
+        hipLaunchKernelGGL((shot_elbo_fwd2_kernel<NHWC, T>), dim3(nblocks(n * Bmax / 4, 1024, 256), 2), dim3(256), 0, s_, P);
         SV_TRY(sv_shot_targets2(a->mu[0], a->ls[0], a->mu[1], a->ls[1], a->la[1], a->label_l, a->perm_l, a->perm_u,
                                 a->lam_l, a->lam_l_dev, a->lam_u, a->lam_u_dev, Bl, Bu, D, K, sm_mu, sm_sigma, lab_mix, mx_mu, mx_sigma, mx_alpha, stream));
         hipLaunchKernelGGL(shot_post_fwd4_kernel, dim3(nblocks((int64_t)Bmax * D, 256, 64), 4), dim3(256), 0, s_, P);
@@ -2538,12 +2773,19 @@ int sv_shot_loss_step2(const sv_shot_loss_args2* a, void* stream) {
         int gx = nblocks(n * Bmax, 256, 2048);                 // (the cls / posterior parts index their elements directly)
         const int need = (int)(((int64_t)Bmax * (D > K ? D : K) + 255) / 256);
         if (gx < need) gx = need;
-        hipLaunchKernelGGL(shot_bwd6_kernel, dim3(gx, 6), dim3(256), 0, s_, P);
+        hipLaunchKernelGGL((shot_bwd6_kernel<NHWC, T>), dim3(gx, 6), dim3(256), 0, s_, P);
         return sv_check_launch("sv_shot_loss_step2");
     }
     // forward: ELBO terms of (1), (3); the targets of (2), (4); their posterior terms; the composition
-    SV_TRY(sv_elbo_fwd(a->image_l, a->rec[0], n, a->mu[0], a->ls[0], a->la[0], Bl, D, K, a->bce, a->x_sigma, a->terms, stream));
-    SV_TRY(sv_elbo_fwd(a->image_u, a->rec[1], n, a->mu[1], a->ls[1], a->la[1], Bu, D, K, a->bce, a->x_sigma, a->terms + 3, stream));
+    typedef shot_rec<NHWC, T> RC;
+    shot_parts Q;                                   // (only what the accessors read)
+    Q.C = io.C; Q.HW = io.HW; Q.ldr = io.ldr; Q.ldd = io.ldd;
+    shot_elbo_part qe[2];
+    for (int i = 0; i < 2; ++i) { qe[i].xr = io.rec[i]; qe[i].dxr = io.d_rec[i]; }
+    { SvProfScope prof_scope(stream);
+      SV_TRY(elbo_fwd_launch(a->image_l, RC::fwd(Q, qe[0]), n, a->mu[0], a->ls[0], a->la[0], Bl, D, K, a->bce, a->x_sigma, a->terms, stream)); }
+    { SvProfScope prof_scope(stream);
+      SV_TRY(elbo_fwd_launch(a->image_u, RC::fwd(Q, qe[1]), n, a->mu[1], a->ls[1], a->la[1], Bu, D, K, a->bce, a->x_sigma, a->terms + 3, stream)); }
     SV_TRY(sv_shot_targets2(a->mu[0], a->ls[0], a->mu[1], a->ls[1], a->la[1], a->label_l, a->perm_l, a->perm_u,
                             a->lam_l, a->lam_l_dev, a->lam_u, a->lam_u_dev, Bl, Bu, D, K, sm_mu, sm_sigma, lab_mix, mx_mu, mx_sigma, mx_alpha, stream));
     SV_TRY(sv_cls_fwd(a->la[2], lab_mix, nullptr, Bl, K, a->terms + 6, stream));
@@ -2552,16 +2794,53 @@ int sv_shot_loss_step2(const sv_shot_loss_args2* a, void* stream) {
     SV_TRY(sv_post_fwd(a->mu[3], a->ls[3], mx_mu, mx_sigma, Bu, D, a->terms + 9, stream));
     SV_TRY(sv_shot_compose(a->terms, &a->sch, a->coef, stream));
     // backward with upstream gradients 1: the coefficients are the `gout` operands; every slice is written once
-    SV_TRY(sv_elbo_bwd(a->image_l, a->rec[0], n, a->mu[0], a->ls[0], a->la[0], Bl, D, K, a->bce, a->x_sigma, a->coef,
-                       a->d_rec[0], a->d_mu[0], a->d_ls[0], a->d_la[0], stream));
-    SV_TRY(sv_elbo_bwd(a->image_u, a->rec[1], n, a->mu[1], a->ls[1], a->la[1], Bu, D, K, a->bce, a->x_sigma, a->coef + 3,
-                       a->d_rec[1], a->d_mu[1], a->d_ls[1], a->d_la[1], stream));
+    { SvProfScope prof_scope(stream);
+      SV_TRY(elbo_bwd_launch(a->image_l, RC::bwd(Q, qe[0]), n, a->mu[0], a->ls[0], a->la[0], Bl, D, K, a->bce, a->x_sigma, a->coef,
+                             a->d_mu[0], a->d_ls[0], a->d_la[0], stream)); }
+    { SvProfScope prof_scope(stream);
+      SV_TRY(elbo_bwd_launch(a->image_u, RC::bwd(Q, qe[1]), n, a->mu[1], a->ls[1], a->la[1], Bu, D, K, a->bce, a->x_sigma, a->coef + 3,
+                             a->d_mu[1], a->d_ls[1], a->d_la[1], stream)); }
     SV_TRY(sv_cls_bwd(lab_mix, nullptr, Bl, K, a->coef + 6, a->d_la[2], stream));
     SV_TRY(sv_post_bwd(a->mu[2], a->ls[2], sm_mu, sm_sigma, Bl, D, a->coef + 7, a->d_mu[2], a->d_ls[2], stream));
     SV_TRY(sv_cls_bwd(mx_alpha, nullptr, Bu, K, a->coef + 8, a->d_la[3], stream));
     SV_TRY(sv_post_bwd(a->mu[3], a->ls[3], mx_mu, mx_sigma, Bu, D, a->coef + 9, a->d_mu[3], a->d_ls[3], stream));
 #undef SV_TRY
     return SV_OK;
+}
+}  // extern "C++"
+
+static int shot_loss_check(const sv_shot_loss_args2* a, const char* who) {
+    SV_REQUIRE(a && a->image_l && a->image_u && a->label_l && a->perm_l && a->perm_u && a->terms && a->coef && a->tgt && a->Bl > 0 &&
+               a->Bu > 0 && a->D > 0 && a->K > 0, SV_E_ARG, "%s: bad argument", who);
+    for (int g = 0; g < 4; ++g)
+        SV_REQUIRE(a->mu[g] && a->ls[g] && a->la[g] && a->d_mu[g] && a->d_ls[g] && a->d_la[g], SV_E_ARG, "%s: group %d: null", who, g);
+    return SV_OK;
+}
+
+int sv_shot_loss_step2(const sv_shot_loss_args2* a, void* stream) {
+    const int rc = shot_loss_check(a, "sv_shot_loss_step2");
+    if (rc != SV_OK) return rc;
+    SV_REQUIRE(a->rec[0] && a->rec[1] && a->d_rec[0] && a->d_rec[1], SV_E_ARG, "sv_shot_loss_step2: reconstruction: null");
+    shot_rec_io io{{a->rec[0], a->rec[1]}, {a->d_rec[0], a->d_rec[1]}, 0, 0, 0, 0};
+    return shot_loss_step_impl<false, float>(a, io, stream);
+}
+
+int sv_shot_loss_step3(const sv_shot_loss_args3* a, void* stream) {
+    SV_REQUIRE(a, SV_E_ARG, "sv_shot_loss_step3: null");
+    const int rc = shot_loss_check(&a->base, "sv_shot_loss_step3");
+    if (rc != SV_OK) return rc;
+    SV_REQUIRE(a->rec[0] && a->rec[1] && a->d_rec[0] && a->d_rec[1], SV_E_ARG, "sv_shot_loss_step3: reconstruction: null");
+    SV_REQUIRE(a->dtype == SV_F32 || a->dtype == SV_BF16, SV_E_ARG, "sv_shot_loss_step3: bad dtype %d", a->dtype);
+    SV_REQUIRE(a->C > 0 && a->HW > 0 && a->ld_rec >= a->C && a->ld_drec >= a->C, SV_E_SHAPE,
+               "sv_shot_loss_step3: C=%d HW=%d ld_rec=%d ld_drec=%d", a->C, a->HW, a->ld_rec, a->ld_drec);
+    SV_REQUIRE(a->base.n_per_img == (int64_t)a->C * a->HW, SV_E_SHAPE, "sv_shot_loss_step3: n_per_img=%lld is not C * HW = %d * %d",
+               (long long)a->base.n_per_img, a->C, a->HW);
+    const int Bmax = a->base.Bl > a->base.Bu ? a->base.Bl : a->base.Bu;
+    SV_REQUIRE(a->base.n_per_img * Bmax < ((int64_t)1 << 31), SV_E_SHAPE, "sv_shot_loss_step3: %d images of %lld elements: too large",
+               Bmax, (long long)a->base.n_per_img);
+    shot_rec_io io{{a->rec[0], a->rec[1]}, {a->d_rec[0], a->d_rec[1]}, a->C, a->HW, a->ld_rec, a->ld_drec};
+    DISPATCH_T(a->dtype, return (shot_loss_step_impl<true, T>(&a->base, io, stream)));
+    return SV_E_ARG;
 }
 
 int sv_mix_lerp(const float* a, const int64_t* index, float lam, const float* lam_dev, int B, int64_t row,
@@ -2572,6 +2851,20 @@ int sv_mix_lerp(const float* a, const int64_t* index, float lam, const float* la
     hipLaunchKernelGGL(mix_lerp_kernel, dim3((unsigned)((row + 255) / 256), B), dim3(256), 0, (hipStream_t)stream, a,
                        index, lam, lam_dev, B, row, exp_space, out);
     return sv_check_launch("sv_mix_lerp");
+}
+
+int sv_mix_pack(int dtype, const float* image_l, const float* image_u, const int64_t* perm_l, const int64_t* perm_u, float lam_l,
+                const float* lam_l_dev, float lam_u, const float* lam_u_dev, int B, int C, int H, int W, int Cpad, void* out,
+                float* sm_img, float* mx_img, void* stream) {
+    SvProfScope prof_scope(stream);
+    SV_REQUIRE(image_l && image_u && perm_l && perm_u && out, SV_E_ARG, "sv_mix_pack: null");
+    SV_REQUIRE(B > 0 && C > 0 && H > 0 && W > 0 && Cpad >= C, SV_E_ARG, "sv_mix_pack: bad shape (B=%d C=%d H=%d W=%d Cpad=%d)", B, C, H, W, Cpad);
+    const int64_t n = 2 * (int64_t)B * H * W;
+    SV_REQUIRE((n + 255) / 256 < ((int64_t)1 << 31), SV_E_SHAPE, "sv_mix_pack: batch too large");
+    DISPATCH_T(dtype, hipLaunchKernelGGL((mix_pack_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                                         image_l, image_u, perm_l, perm_u, lam_l, lam_l_dev, lam_u, lam_u_dev, B, C, H * W, Cpad, (T*)out,
+                                         sm_img, mx_img));
+    return sv_check_launch("sv_mix_pack");
 }
 
 int sv_optimal_match(const float* mu, const float* ls, int B, int D, int64_t* index, void* stream) {

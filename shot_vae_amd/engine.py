@@ -573,6 +573,11 @@ class Engine:
         return ws
 
     wgrad_side_stream = True      # weight gradients on a side stream (they are off the backward's critical path)
+    # the step's glue in fused launches: every group's sampler in one grid (sv_sample_fwd_groups / _bwd_groups) and, in the grouped
+    # step's single-launch plan, the input side as one kernel (sv_mix_pack) and the loss stage on the decoder's NHWC logits
+    # (sv_shot_loss_step3: no NCHW round trip of the reconstruction and its gradient).  False: the per-group / per-tensor chain,
+    # which computes the same bits (tests/test_glue_fusion_gpu.py)
+    fused_glue = True
     sparse_shortcut_grad = True      # stride-2 1x1 shortcuts: data gradient written / read at the even positions only
     compact_shortcut_grad = True     # ... as a dense 1x1 product over the stride-2 grid, stored compactly (bf16)
     materialize_decoder_act = True   # BatchNorm + ReLU of the first decoder layers' inputs as a pass of its own (see forward)
@@ -989,14 +994,45 @@ class Engine:
                              "(one per group)" % G)
         return keys.contiguous()
 
+    def _sample_table(self, groups, B, u=None):
+        """the sv_sample_group table of a launch of len(groups) groups of B rows (sv_sample_fwd_groups / _bwd_groups); the
+        library reads it during the call, the tensors it points into are the caller's (the forward context keeps them)"""
+        tab = (L.SvSampleGroup * len(groups))()
+        for gi, (mode, label, label_mix, lam) in enumerate(groups):
+            g = tab[gi]
+            g.mode, g.row0, g.rows = int(mode), gi * B, B
+            if u is not None and mode == 0:
+                g.u = u[gi * B:].data_ptr()
+            if label is not None:
+                g.label = label.data_ptr()
+            if label_mix is not None:
+                g.label_mix = label_mix.data_ptr()
+            if torch.is_tensor(lam):
+                g.lam_dev = lam.data_ptr()
+            else:
+                g.lam = float(lam)
+        return tab
+
+    def rec_nchw(self, f):
+        """the reconstruction logits of forward context `f` as fp32 NCHW [Gd * B, C, H, W] (None without reconstructed groups):
+        the conversion Engine.forward(..., want_rec=False) left out"""
+        p = self.plan
+        if f.Gd == 0:
+            return None
+        n = f.Gd * f.B
+        rec = torch.empty(n, p.in_ch, p.img, p.img, dtype=torch.float32, device=f.h[5].device)
+        L.call("sv_nhwc_to_nchw", self.code, _vp(f.h[5].data_ptr()), n, p.in_ch, p.img, p.img, p.dec_convs[5].N,
+               _vp(rec.data_ptr()), self._stream())
+        return rec
+
     def forward(self, image, groups, eps, u, temperature, training, keep, rec_groups=None, update_order=None, x16=None,
-                keys=None):
+                keys=None, want_rec=True):
         """One BATCHED forward of G = len(groups) independent instances of the network that share the weights (the
         forwards (1)-(4) of a SHOT-VAE step, main_shot_vae.py:288,311,329,356, or a single one): every launch carries
         the G groups (sv_igemm_args::groups), each with its OWN BatchNorm batch statistics -- the reference's
         semantics of separate model(...) calls -- so the step costs a quarter of the launches at four times the rows.
 
-        image   NCHW fp32 on device, [G * B] images: the groups back to back, B images each
+        image   NCHW fp32 on device, [G * B] images: the groups back to back, B images each; None when x16 is given
         groups  list of (mode, label, label_mix, lam): the sampler mode of each group (vae.py:38-52): 0 Gumbel-softmax,
                 1 one-hot(label), 2 lam * onehot(label) + (1 - lam) * onehot(label_mix)
         eps, u  [G * B, ldc] Gaussian noise, [G * B, K] uniform noise (rows of groups with mode != 0 are ignored) or None
@@ -1010,7 +1046,11 @@ class Engine:
                 grouped step converts on its input-side stream, beside the previous step's backward
         keys    dropout (drop_rate > 0, training only): int64 [G] device tensor, the mask key of each group (sv_dropout_args);
                 ignored in eval mode, where dropout is the identity
+        want_rec  False: rec is not converted to NCHW fp32 (returned as None) -- the caller reads the logits from ctx.h[5], the
+                last ConvTranspose's NHWC output (the grouped step's loss stage; Engine.rec_nchw converts on demand)
         Returns (rec NCHW fp32, mu, ls, la, ctx-or-None), all [G * B, ...]."""
+        if image is None:
+            image = x16                    # (only its batch size and device are used below)
         self._require_gpu(image)
         p = self.plan
         G = len(groups)
@@ -1025,7 +1065,8 @@ class Engine:
         T = self.tdtype
         st = self._stream()
         self.ensure_packs()
-        image = image.contiguous().float()
+        if x16 is None:
+            image = image.contiguous().float()
         pbase = self.param.data_ptr()
         pk, es = self.packs.data_ptr(), self.packs.element_size()
         fs = self._fwd_scratch(B, G, training, dev)
@@ -1044,8 +1085,13 @@ class Engine:
                _vp(la.data_ptr()), st)
         latent = torch.empty(Bt, p.Lpad, dtype=T, device=dev)
         csoft = torch.empty(Bt, p.K, dtype=torch.float32, device=dev)
-        for gi, (mode, label, label_mix, lam) in enumerate(groups):      # the sampler mode differs per group (vae.py:38-52)
-            r0 = gi * B
+        one_grid = self.fused_glue and G <= L.MAX_SAMPLE_GROUPS
+        if one_grid:                                                     # every group's sampler in one grid
+            tab = self._sample_table(groups, B, u)
+            L.call("sv_sample_fwd_groups", self.code, _vp(mu.data_ptr()), _vp(ls.data_ptr()), _vp(la.data_ptr()), _vp(eps.data_ptr()),
+                   tab, G, float(temperature), p.ldc, p.K, p.Lpad, _vp(latent.data_ptr()), _vp(csoft.data_ptr()), st)
+        for gi, (mode, label, label_mix, lam) in enumerate(() if one_grid else groups):
+            r0 = gi * B                                                   # the sampler mode differs per group (vae.py:38-52)
             L.call("sv_sample_fwd", self.code, _vp(mu[r0:].data_ptr()), _vp(ls[r0:].data_ptr()), _vp(la[r0:].data_ptr()),
                    _vp(eps[r0:].data_ptr()), _vp(u[r0:].data_ptr()) if (u is not None and mode == 0) else None,
                    _vp(label.data_ptr()) if label is not None else None,
@@ -1054,11 +1100,7 @@ class Engine:
                    mode, float(temperature), B, p.ldc, p.K, p.Lpad, _vp(latent[r0:].data_ptr()),
                    _vp(csoft[r0:].data_ptr()), st)
         self._decoder_forward(fs, f, latent, Gd)
-        rec = None
-        if Gd > 0:
-            rec = torch.empty(Gd * B, p.in_ch, p.img, p.img, dtype=torch.float32, device=dev)
-            L.call("sv_nhwc_to_nchw", self.code, _vp(f.h[5].data_ptr()), Gd * B, p.in_ch, p.img, p.img, p.dec_convs[5].N,
-                   _vp(rec.data_ptr()), st)
+        rec = self.rec_nchw(f) if want_rec else None
         self._finish_forward(fs, f, training, update_order)
         if not keep:
             return rec, mu, ls, la, None
@@ -1284,6 +1326,26 @@ class Engine:
                _vp(x16.data_ptr()), self._stream())
         return x16
 
+    def mix_pack(self, image_l, image_u, perm_l, perm_u, lam_l, lam_u, keep_mixed=False):
+        """The input side of the single-launch step in one kernel (sv_mix_pack): the stem's NHWC16 tensor of the four groups
+        image_l | image_u | lerp(image_l, perm_l, lam_l) | lerp(image_u, perm_u, lam_u), [4 B, H, W, 16] in the compute dtype --
+        the bits of mixup._lerp x 2, torch.cat and to_nhwc16.  lam_*: float or device scalar.  keep_mixed: also return the two
+        mixed batches as fp32 NCHW (else None).  Returns (x16, sm_img, mx_img)."""
+        p = self.plan
+        self._require_gpu(image_l)
+        image_l, image_u = image_l.contiguous().float(), image_u.contiguous().float()
+        B = image_l.shape[0]
+        assert image_u.shape == image_l.shape and perm_l.numel() == B and perm_u.numel() == B
+        x16 = torch.empty(4 * B, p.img, p.img, CPAD, dtype=self.tdtype, device=image_l.device)
+        sm = torch.empty_like(image_l) if keep_mixed else None
+        mx = torch.empty_like(image_u) if keep_mixed else None
+        ptr = lambda t: _vp(t.data_ptr()) if t is not None else None
+        dl, du = torch.is_tensor(lam_l), torch.is_tensor(lam_u)
+        L.call("sv_mix_pack", self.code, ptr(image_l), ptr(image_u), ptr(perm_l), ptr(perm_u), 0.0 if dl else float(lam_l),
+               ptr(lam_l) if dl else None, 0.0 if du else float(lam_u), ptr(lam_u) if du else None, B, p.in_ch, p.img, p.img, CPAD,
+               ptr(x16), ptr(sm), ptr(mx), self._stream())
+        return x16, sm, mx
+
     def _bn_counts(self, B):
         """samples per channel of every BatchNorm (in plan order) for batch size B"""
         cnt = {b.index: float(rows) for b, rows in self._bn_rows(B)}
@@ -1334,10 +1396,11 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------------------- backward
-    def backward(self, f, d_rec, d_mu, d_ls, d_la, own_grads=False):
+    def backward(self, f, d_rec, d_mu, d_ls, d_la, own_grads=False, d_rec_nhwc=False):
         """Gradients accumulate (+=) into self.grad; nothing is returned (inputs need no grad).  Batched like the
-        forward it belongs to: every launch carries the G groups, the weight gradients sum over them."""
-        self._guarded(self._backward, f, d_rec, d_mu, d_ls, d_la, own_grads)
+        forward it belongs to: every launch carries the G groups, the weight gradients sum over them.  d_rec: fp32 NCHW, or
+        (d_rec_nhwc) NHWC [Gd * B, H, W, dec_convs[5].N] in the compute dtype with zero padding channels, used as it is."""
+        self._guarded(self._backward, f, d_rec, d_mu, d_ls, d_la, own_grads, d_rec_nhwc)
 
     def _guarded(self, backward_fn, *args):
         try:
@@ -1441,7 +1504,7 @@ class Engine:
         return types.SimpleNamespace(bsums=bsums, bs_off=bs_off, bs_rep=bs_rep, det=det, det_keep=det_keep, bnp=bnp, ex_of=ex_of,
                                      bn_apply=bn_apply, bn_fold=bn_fold, bn_affine=bn_affine)
 
-    def _backward(self, f, d_rec, d_mu, d_ls, d_la, own_grads=False):
+    def _backward(self, f, d_rec, d_mu, d_ls, d_la, own_grads=False, d_rec_nhwc=False):
         p = self.plan
         B, G, T = f.B, f.G, self.tdtype
         Bt = B * G
@@ -1468,9 +1531,13 @@ class Engine:
         dmu, dls, dla = mine(d_mu, f.mu), mine(d_ls, f.ls), mine(d_la, f.la)
         if Gd > 0:
             last = p.dec_convs[5]
-            D = torch.empty(Bd, p.img, p.img, last.N, dtype=T, device=dev)
-            L.call("sv_nchw_to_nhwc", self.code, _vp(d_rec.data_ptr()), Bd, p.in_ch, p.img, p.img, last.N,
-                   _vp(D.data_ptr()), st)
+            if d_rec_nhwc:                    # already the tensor the decoder's backward reads (the NHWC loss stage wrote it)
+                assert d_rec.dtype == T and tuple(d_rec.shape) == (Bd, p.img, p.img, last.N) and d_rec.is_contiguous()
+                D = d_rec
+            else:
+                D = torch.empty(Bd, p.img, p.img, last.N, dtype=T, device=dev)
+                L.call("sv_nchw_to_nhwc", self.code, _vp(d_rec.data_ptr()), Bd, p.in_ch, p.img, p.img, last.N,
+                       _vp(D.data_ptr()), st)
             for i in range(5, 0, -1):
                 cv, b = p.dec_convs[i], p.dec_bns[i - 1]
                 hin = f.h[i - 1][:Bd]                     # the groups are back to back: the first Gd are a prefix
@@ -1493,7 +1560,13 @@ class Engine:
                                                        groups=Gd))
             # ---- sampler (the latent's gradient reaches mu / log_sigma / log_alpha) -------------------------------
             dl2 = dlat.view(Bd, p.Lpad)
-            for gi, (mode, _, _, _) in enumerate(f.groups[:Gd]):
+            fused = self.fused_glue and Gd <= L.MAX_SAMPLE_GROUPS
+            if fused:
+                tab = self._sample_table([(g[0], None, None, 0.0) for g in f.groups[:Gd]], B)
+                L.call("sv_sample_bwd_groups", self.code, _vp(dl2.data_ptr()), _vp(f.ls.data_ptr()), _vp(f.eps.data_ptr()),
+                       _vp(f.csoft.data_ptr()), tab, Gd, float(f.temperature), p.ldc, p.K, p.Lpad, _vp(dmu.data_ptr()),
+                       _vp(dls.data_ptr()), _vp(dla.data_ptr()), st)
+            for gi, (mode, _, _, _) in enumerate(() if fused else f.groups[:Gd]):
                 r0 = gi * B
                 L.call("sv_sample_bwd", self.code, _vp(dl2[r0:].data_ptr()), _vp(f.ls[r0:].data_ptr()),
                        _vp(f.eps[r0:].data_ptr()), _vp(f.csoft[r0:].data_ptr()), mode, float(f.temperature), B, p.ldc, p.K,

@@ -113,33 +113,39 @@ class _ShotLossFn(torch.autograd.Function):
         return (d_rec, d_mu, d_ls, d_la) + (None,) * 10
 
 
-def shot_loss_step_groups(outs, grads, image_l, image_u, label_l, perm_l, perm_u, lam_l, lam_u, sch, bce=True, x_sigma=1.0):
+def shot_loss_step_groups(outs, grads, image_l, image_u, label_l, perm_l, perm_u, lam_l, lam_u, sch, bce=True, x_sigma=1.0,
+                          nhwc=None):
     """The loss stage WITHOUT autograd, for a step that drives the network's backward itself (train_step_grouped): the
     forward reductions and, with upstream gradients 1 for both objectives (`(loss_sup + loss_unsup).backward()`), the
     gradients w.r.t. the network outputs -- 9 + 6 launches issued back to back by ONE call into the library
     (sv_shot_loss_step2: at ~5 us per kernel the stage is bound by the per-launch host time of a Python caller).
     outs[i] = (rec or None, mu, ls, la) of forward i in (1, 2, 3, 4), grads[i] = (d_rec or None, d_mu, d_ls, d_la): the
     tensors the gradients are WRITTEN to (row slices of whatever the caller's launches need; forwards (1), (2) have B_l
-    rows, (3), (4) B_u rows).  Returns terms[12]."""
+    rows, (3), (4) B_u rows).
+    nhwc = (dtype code, C): outs[i][0] / grads[i][0] of forwards (1), (3) are the decoder's NHWC logits [B, H, W, ld] and the NHWC
+    gradient its backward reads ([B, H, W, ld'], padding channels zeroed here), both in the compute dtype (sv_shot_loss_step3:
+    the same terms and gradients, bit for bit, as the fp32 NCHW form on the converted tensors).  Returns terms[12]."""
     Bl, Bu, D, K = image_l.shape[0], image_u.shape[0], outs[1][1].shape[1], outs[1][3].shape[1]
     for i in (1, 2, 3, 4):
-        for t in outs[i] + grads[i]:
+        for j, t in enumerate(outs[i] + grads[i]):
             if t is None:
                 continue
             if not t.is_cuda:
                 raise L.ShotVaeHipError("shot_vae_amd losses run on an MI355X only (no CPU fallback)")
-            assert t.is_contiguous() and t.dtype == torch.float32 and t.shape[0] == (Bl if i < 3 else Bu), (i, t.shape, t.dtype)
+            f32 = torch.float32 if (nhwc is None or j % 4) else t.dtype       # (j % 4 == 0: the reconstruction / its gradient)
+            assert t.is_contiguous() and t.dtype == f32 and t.shape[0] == (Bl if i < 3 else Bu), (i, t.shape, t.dtype)
     f32 = dict(dtype=torch.float32, device=image_l.device)
     image_l, image_u = image_l.contiguous().float(), image_u.contiguous().float()
     label_l = label_l.long().contiguous()
     terms = torch.zeros(12, **f32)
     scratch = torch.empty(10 + 2 * (Bl + Bu) * D + (Bl + Bu) * K, **f32)          # coef | the targets
-    a = L.SvShotLossArgs2()
+    a3 = L.SvShotLossArgs3()
+    a = a3.base
     for slot, i in enumerate((1, 3, 2, 4)):                 # the library's group order
         a.mu[slot], a.ls[slot], a.la[slot] = (t.data_ptr() for t in outs[i][1:])
         a.d_mu[slot], a.d_ls[slot], a.d_la[slot] = (t.data_ptr() for t in grads[i][1:])
     for slot, i in enumerate((1, 3)):
-        a.rec[slot], a.d_rec[slot] = outs[i][0].data_ptr(), grads[i][0].data_ptr()
+        (a if nhwc is None else a3).rec[slot], (a if nhwc is None else a3).d_rec[slot] = outs[i][0].data_ptr(), grads[i][0].data_ptr()
     a.image_l, a.image_u, a.label_l = image_l.data_ptr(), image_u.data_ptr(), label_l.data_ptr()
     a.perm_l, a.perm_u = perm_l.data_ptr(), perm_u.data_ptr()
     keep = []
@@ -152,7 +158,14 @@ def shot_loss_step_groups(outs, grads, image_l, image_u, label_l, perm_l, perm_u
     a.Bl, a.Bu, a.D, a.K, a.bce, a.n_per_img, a.x_sigma = Bl, Bu, D, K, int(bce), image_l[0].numel(), float(x_sigma)
     a.sch = L.SvShotSchedule(*[float(sch[k]) for k in ("ew", "kl_beta_c", "kl_beta_d", "cmi", "dmi", "pwm", "ucw")])
     a.terms, a.coef, a.tgt = terms.data_ptr(), scratch.data_ptr(), scratch.data_ptr() + 40
-    L.call("sv_shot_loss_step2", C.byref(a), _st())
+    if nhwc is None:
+        L.call("sv_shot_loss_step2", C.byref(a), _st())
+        return terms
+    r, d = outs[1][0], grads[1][0]
+    assert r.dim() == 4 and d.dim() == 4 and r.shape[1:3] == d.shape[1:3] and outs[3][0].shape[1:] == r.shape[1:] \
+        and grads[3][0].shape[1:] == d.shape[1:]
+    a3.dtype, a3.C, a3.HW, a3.ld_rec, a3.ld_drec = int(nhwc[0]), int(nhwc[1]), r.shape[1] * r.shape[2], r.shape[3], d.shape[3]
+    L.call("sv_shot_loss_step3", C.byref(a3), _st())
     return terms
 
 

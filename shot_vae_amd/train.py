@@ -246,7 +246,7 @@ def train_step_grouped(model, elbo_criterion, cls_criterion, optimizer, image_l,
     try:
         with step_range("inputs"):
             prep = _grouped_inputs(model, image_l, label_l, image_u, epsilon, device_rng, optimal_match, launches,
-                                   side_in is not None)
+                                   side_in is not None, return_outputs)
     finally:
         if side_in is not None:
             torch.cuda.set_stream(main)
@@ -259,9 +259,11 @@ def train_step_grouped(model, elbo_criterion, cls_criterion, optimizer, image_l,
                          label_u, return_outputs, optimal_match, launches, prep)
 
 
-def _grouped_inputs(model, image_l, label_l, image_u, epsilon, device_rng, optimal_match, launches, whole):
+def _grouped_inputs(model, image_l, label_l, image_u, epsilon, device_rng, optimal_match, launches, whole, keep_mixed=True):
     """The input side of a grouped step: every random draw in the reference's order, the smoothed labelled batch and -- for
-    the single-launch plan when `whole` -- the mixed unlabelled batch, the concatenated images and their NHWC16 form."""
+    the single-launch plan when `whole` -- the mixed unlabelled batch, the concatenated images and their NHWC16 form.
+    With Engine.fused_glue the single-launch plan gets its NHWC16 batch from ONE kernel (Engine.mix_pack), whether `whole` or
+    not: neither mixed batch nor the concatenation exists as a tensor then, unless `keep_mixed` asks for sm_img / mx_img."""
     plan = model._plan
     K, ldc = plan.K, plan.ldc
     Bl, Bu = image_l.size(0), image_u.size(0)
@@ -328,14 +330,21 @@ def _grouped_inputs(model, image_l, label_l, image_u, epsilon, device_rng, optim
             lam_u = np.random.beta(2.0, 2.0)
     perm_l = perm_l.long().contiguous()
     model._last_lams = (lam_l, lam_u)          # (data-parallel runs check that every rank used the same pair)
+    pack = eng.fused_glue and len(launches) == 1 and len(launches[0]) == 4 and image_l.is_cuda
+    mx_img = image_cat = x16 = None
     with torch.no_grad():
-        sm_img = _lerp(image_l, perm_l, lam_l, False)                        # mixup.py:36
+        if pack:                                                             # mixup.py:36 and :22, and the stem's input layout
+            perm_u = perm_u.long().contiguous()
+            x16, sm_img, mx_img = eng.mix_pack(image_l, image_u, perm_l, perm_u, lam_l, lam_u, keep_mixed)
+        else:
+            sm_img = _lerp(image_l, perm_l, lam_l, False)                    # mixup.py:36
         sm_label = label_l[perm_l]
     images = {1: image_l, 2: sm_img, 3: image_u}
+    if pack:
+        images[4] = mx_img
     specs = {1: dict(disc_label=label_l), 3: dict(), 4: dict(),
              2: dict(mixup=True, disc_label=label_l, disc_pseudo_label=sm_label, mixup_lam=lam_l)}
-    mx_img = image_cat = x16 = None
-    if whole:
+    if whole and not pack:
         with torch.no_grad():
             perm_u = perm_u.long().contiguous()
             mx_img = images[4] = _lerp(image_u, perm_u, lam_u, False)            # mixup.py:22
@@ -343,7 +352,7 @@ def _grouped_inputs(model, image_l, label_l, image_u, epsilon, device_rng, optim
             x16 = eng.to_nhwc16(image_cat)
     return dict(eps=eps, u=u, e_all=e_all, u_all=u_all, device_noise=device_noise, perm_l=perm_l, perm_u=perm_u, lam_l=lam_l,
                 lam_u=lam_u, sm_img=sm_img, sm_label=sm_label, images=images, specs=specs, mx_img=mx_img, image_cat=image_cat,
-                x16=x16, keys=keys, keys_all=keys_all,
+                x16=x16, keys=keys, keys_all=keys_all, pack=pack,
                 tensors=[e_all, u_all, perm_l, perm_u, sm_img, sm_label, mx_img, image_cat, x16, lam_l, lam_u, keys_all] +
                 list(eps.values()) + list(u.values()) + list(keys.values()))
 
@@ -364,8 +373,10 @@ def _grouped_body(model, elbo_criterion, cls_criterion, optimizer, image_l, labe
     # fixed ((loss_sup + loss_unsup).backward() = upstream gradients 1), and the autograd engine's worker-thread hand-over
     # left the GPU idle between the loss kernels and the network's backward
     outs, ctxs = {}, []
+    # fused glue (single-launch plan): the loss stage reads the decoder's NHWC logits and writes the NHWC gradient its backward reads
+    nhwc = prep["pack"]
     for li, ids in enumerate(launches):
-        if 4 in ids and mx_img is None:
+        if 4 in ids and mx_img is None and not prep["pack"]:
             with torch.no_grad():
                 if optimal_match:                                            # mixup.py:9-18 on the outputs of forward (3)
                     perm_u = optimal_match_index(outs[3][1], outs[3][2])
@@ -397,9 +408,11 @@ def _grouped_body(model, elbo_criterion, cls_criterion, optimizer, image_l, labe
                                                                     u=u_cat, rec_groups=nrec, update_order=order,
                                                                     image_cat=prep["image_cat"] if len(launches) == 1 else None,
                                                                     x16=prep["x16"] if len(launches) == 1 else None,
-                                                                    keys=k_cat)
+                                                                    keys=k_cat, want_rec=not nhwc)
         finally:
             eng.defer_slot = None
+        if nhwc:
+            rec = fctx.h[5]                                                  # [nrec * B, H, W, ld] in the compute dtype
         ctxs.append((ids, fctx, rec, mu, ls, la))
         for j, k in enumerate(ids):
             outs[k] = (rec[j * B:(j + 1) * B] if j < nrec else None, mu[j * B:(j + 1) * B], ls[j * B:(j + 1) * B],
@@ -417,7 +430,8 @@ def _grouped_body(model, elbo_criterion, cls_criterion, optimizer, image_l, labe
             grads[k] = (d[0][j * B:(j + 1) * B] if outs[k][0] is not None else None,) + tuple(t[j * B:(j + 1) * B] for t in d[1:])
     with step_range("loss"):
         terms = shot_loss_step_groups(outs, grads, image_l, image_u, label_l, perm_l, perm_u, lam_l, lam_u, sch,
-                                      bce=elbo_criterion.bce_reconstruction, x_sigma=elbo_criterion.x_sigma)
+                                      bce=elbo_criterion.bce_reconstruction, x_sigma=elbo_criterion.x_sigma,
+                                      nhwc=(eng.code, plan.in_ch) if nhwc else None)
     loss_sup, loss_unsup = terms[10], terms[11]
     # backward(s): launches without a reconstruction first; the decoder-first gradient bucket of a data-parallel step is armed
     # for the LAST backward that runs the decoder (its gradients are complete once that one has issued them)   :324 + :364
@@ -426,7 +440,7 @@ def _grouped_body(model, elbo_criterion, cls_criterion, optimizer, image_l, labe
         if n == len(seq) - 1 and optimizer is not None and _bucketed(model, distributed) is not None:
             _bucketed(model, distributed).arm()
         with step_range("backward"):
-            model.backward_direct(ctxs[i][1], *per_launch[i], own_grads=True)
+            model.backward_direct(ctxs[i][1], *per_launch[i], own_grads=True, d_rec_nhwc=nhwc)
     if optimizer is not None:
         with step_range("update"):
             apply_update(model, optimizer, distributed)
@@ -435,6 +449,9 @@ def _grouped_body(model, elbo_criterion, cls_criterion, optimizer, image_l, labe
             return loss_sup.detach(), loss_unsup.detach(), kl_inference
         return loss_sup.detach(), loss_unsup.detach()
     res = {k: terms[i].detach() for i, k in enumerate(TERMS)}
+    if nhwc:                                  # the reconstructions as the API's fp32 NCHW tensors, on demand
+        rec13 = eng.rec_nchw(ctxs[0][1])
+        outs[1], outs[3] = (rec13[:Bl],) + outs[1][1:], (rec13[Bl:],) + outs[3][1:]
     res.update(sm_img=sm_img, mx_img=mx_img, rec1=outs[1][0], rec3=outs[3][0], perm_u=perm_u)
     for i in (1, 2, 3, 4):
         for n, t in zip(("mu", "ls", "la"), outs[i][1:]):

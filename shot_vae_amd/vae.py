@@ -332,30 +332,32 @@ class VariationalAutoEncoder(FlatModule):
         return self._run(torch.cat([im.float() for im in images]), gs, eps, u, rec_groups, update_order, keys)
 
     def forward_groups_direct(self, images, specs, eps, u, rec_groups=None, update_order=None, image_cat=None, x16=None,
-                              keys=None):
+                              keys=None, want_rec=True):
         """forward_groups for a caller that runs the backward itself (no autograd node): returns (rec, mu, ls, la, ctx); pass
         ctx and the gradients w.r.t. the four outputs to backward_direct().  image_cat / x16: the concatenated images and
-        their NHWC16 form when the caller has already made them (train_step_grouped's input-side stream).  keys: the dropout
-        keys (int64 [G] on the device), required in training mode with drop_rate > 0."""
+        their NHWC16 form when the caller has already made them (train_step_grouped's input-side stream); with x16 alone the
+        images are not concatenated (and `images` is not read).  keys: the dropout keys (int64 [G] on the device), required in
+        training mode with drop_rate > 0.  want_rec=False: rec is None, the logits stay in ctx.h[5] (Engine.forward)."""
         gs = [self._group_spec(sp.get("mixup", False), sp.get("disc_label"), sp.get("disc_pseudo_label"),
                                sp.get("mixup_lam")) for sp in specs]
         with torch.no_grad():
-            if image_cat is None:
+            if image_cat is None and x16 is None:
                 image_cat = torch.cat([im.float() for im in images])
             if self._drop_active():
                 self._log_keys(keys)
             return self._engine.forward(image_cat, gs, eps, u, self._temperature, self.training, keep=True,
                                         rec_groups=rec_groups, update_order=update_order, x16=x16,
-                                        keys=keys if self._drop_active() else None)
+                                        keys=keys if self._drop_active() else None, want_rec=want_rec)
 
-    def backward_direct(self, ctx, d_rec, d_mu, d_ls, d_la, own_grads=False):
+    def backward_direct(self, ctx, d_rec, d_mu, d_ls, d_la, own_grads=False, d_rec_nhwc=False):
         """accumulates the parameter gradients of a forward_groups_direct() call into the flat gradient buffer (p.grad).
-        own_grads: d_mu / d_ls / d_la are the caller's own, freshly written tensors and may be modified in place"""
+        own_grads: d_mu / d_ls / d_la are the caller's own, freshly written tensors and may be modified in place;
+        d_rec_nhwc: d_rec is the NHWC gradient of the decoder's last layer (Engine.backward)"""
         if not ctx.training:
             raise NotImplementedError("backward through an eval-mode forward (BatchNorm with running statistics) is not implemented")
         self._attach_grads()
         with torch.no_grad():
-            self._engine.backward(ctx, d_rec, d_mu, d_ls, d_la, own_grads)
+            self._engine.backward(ctx, d_rec, d_mu, d_ls, d_la, own_grads, d_rec_nhwc)
 
     # ------------------------------------------------------------------ inference API (eval mode only; extension)
     # The halves of the eval-mode forward as calls of their own (Engine.encode / latent_draw / decode).  BatchNorm normalises with
