@@ -332,7 +332,7 @@ def check_flag_timeouts(where=""):
     """Fail closed on the device-side fork (sv_stream_wait_flag): a wait that gave up let a weight gradient read operands that
     were not written yet -- the gradients of that step (and, after an all-reduce, of every rank) are garbage.  The counter is
     sticky and lives in host-mapped memory: reading it costs neither a copy nor a synchronisation, so every step checks it
-    (Engine._join_side, FlatSGD.step, dp's all-reduce); a time-out that has not been executed yet is caught one step later."""
+    (WgradSideStream.join, FlatSGD.step, dp's all-reduce); a time-out that has not been executed yet is caught one step later."""
     n = lib().sv_flag_timeouts()
     if n:
         raise ShotVaeHipError(

@@ -132,7 +132,7 @@ class DecoderFirstAllReduce:
             if self.comm is None:
                 self.comm = torch.cuda.Stream()
             self.comm.wait_stream(cur)
-            side = getattr(eng, "_side_streams", {}).get(cur.cuda_stream)      # the decoder's weight gradients run there
+            side = eng._side.side_of(cur)      # the decoder's weight gradients run there
             if side is not None:
                 self.comm.wait_stream(side)
             with torch.cuda.stream(self.comm):

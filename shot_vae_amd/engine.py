@@ -24,6 +24,8 @@ import torch
 
 from . import _lib as L
 from . import geometry as G
+from .geometry import ConvSpec
+from .sidestream import WgradSideStream
 _GEOM = G          # (functions below use G for the number of groups)
 
 LEAKY_SLOPE = 0.01     # nn.LeakyReLU default, wideresnet.py:28
@@ -72,54 +74,6 @@ def encoder_family(name):
         return dict(stem=64, widths=[64, 128, 256, 512], units=list(units), slope=0.0, slope_i=1.0,
                     block="block%d.preact_block.", unit="unit%d.")
     raise NotImplementedError("{} not implemented".format(name))
-
-
-class ConvSpec:
-    """One conv-like layer (Conv2d / ConvTranspose2d / the k=1 ConvTranspose GEMM)."""
-
-    def __init__(self, key, kind, k, stride, pad, cin, n, hin, cin_real=None, n_real=None):
-        self.key, self.kind, self.k, self.stride, self.pad = key, kind, k, stride, pad
-        self.Cin, self.N, self.Hin = cin, n, hin
-        self.cin_real, self.n_real = cin_real or cin, n_real or n
-        self.T = k * k
-        self.master_off = None
-        self.fwd_off = self.dgrad_off = None
-        self._g = {}
-
-    @property
-    def Hout(self):
-        if self.kind == "conv":
-            return (self.Hin + 2 * self.pad - self.k) // self.stride + 1
-        return self.Hin * self.stride
-
-    def geom_fwd(self, B):
-        g = self._g.get(("f", B))
-        if g is None:
-            if self.kind == "conv":
-                g = G.conv_like(B, self.Hin, self.Hin, self.Cin, self.N, self.k, self.stride, self.pad)
-            else:
-                g = G.convT_like(B, self.Hin, self.Hin, self.Cin, self.N, self.k, self.stride, self.pad)
-            self._g[("f", B)] = g
-        return g
-
-    def geom_dgrad(self, B):
-        """input = gradient w.r.t. this layer's output, output = gradient w.r.t. its input."""
-        g = self._g.get(("d", B))
-        if g is None:
-            ho = self.Hout
-            if self.kind == "conv":
-                g = G.convT_like(B, ho, ho, self.N, self.Cin, self.k, self.stride, self.pad)
-            else:
-                g = G.conv_like(B, ho, ho, self.N, self.Cin, self.k, self.stride, self.pad)
-            self._g[("d", B)] = g
-        return g
-
-    def torch_view(self, master):
-        """The reference-shaped (OIHW for Conv2d, IOHW for ConvTranspose2d) strided view."""
-        m = master[self.master_off: self.master_off + self.N * self.T * self.Cin].view(self.N, self.k, self.k, self.Cin)
-        if self.kind == "conv":
-            return m.permute(0, 3, 1, 2)[: self.n_real, : self.cin_real]
-        return m.permute(3, 0, 1, 2)[: self.cin_real, : self.n_real]
 
 
 class BNSpec:
@@ -340,7 +294,6 @@ class Engine:
         self.packs = None
         self._pack_key = None
         self._manual_epoch = 0
-        self.use_tr = 1
         self.prof_tags = None
         self.prof_cost = {}
         self.defer_slot = None        # k: this forward's running-stat update is deferred into slot k (apply_pending)
@@ -365,8 +318,8 @@ class Engine:
         # bench.py's per-launch timing pass issues the step on ONE stream (HIP events bracket every launch); with this set it
         # still gives the paired launches the block budgets they run with in the timed, two-stream step
         self.prof_paired = False
-        self._side_keep = {}          # main stream -> operands of the weight gradients in flight on its side stream
-        self._pending_wgrads = []     # weight gradients waiting for the next fork (fork_every)
+        self._side = WgradSideStream(self)      # the weight gradients' side stream: the fork / join schedule and its state
+        self._ws = {}                 # (stream, device) -> wgrad partial-slab workspace
         for b in p.bns:
             self.bufs[b.rv_off: b.rv_off + b.C] = 1.0
 
@@ -555,21 +508,17 @@ class Engine:
                 a.bsums, a.replicas = ex[6:]
         if tag:
             self._tag(tag, g, (residual is not None) + (ex is not None), groups=groups)
-        if self._start_signal is not None:       # (see _wgrad_async: this launch forks the side stream when it starts)
-            (a.start_flag, a.start_value), self._start_signal = self._start_signal, None
+        a.start_flag, a.start_value = self._side.take_start_signal() or (None, 0)      # (WgradSideStream.submit: this launch then forks the side stream)
         L.call("sv_igemm", C.byref(g), self.code, C.byref(a), self._stream())
 
     _ws_elems = 16 * 1024 * 1024       # 64 MiB of fp32 partial-slab workspace for sv_wgrad
 
     def _wg_ws(self):
         """wgrad partial-slab workspace, one per stream (two backwards may run concurrently)."""
-        pool = getattr(self, "_ws", None)
-        if pool is None:
-            pool = self._ws = {}
         key = (torch.cuda.current_stream().cuda_stream, self.param.device)
-        ws = pool.get(key)
+        ws = self._ws.get(key)
         if ws is None:
-            ws = pool[key] = torch.empty(self._ws_elems, dtype=torch.float32, device=self.param.device)
+            ws = self._ws[key] = torch.empty(self._ws_elems, dtype=torch.float32, device=self.param.device)
         return ws
 
     wgrad_side_stream = True      # weight gradients on a side stream (they are off the backward's critical path)
@@ -578,10 +527,9 @@ class Engine:
     # (sv_shot_loss_step3: no NCHW round trip of the reconstruction and its gradient).  False: the per-group / per-tensor chain,
     # which computes the same bits (tests/test_glue_fusion_gpu.py)
     fused_glue = True
-    sparse_shortcut_grad = True      # stride-2 1x1 shortcuts: data gradient written / read at the even positions only
-    compact_shortcut_grad = True     # ... as a dense 1x1 product over the stride-2 grid, stored compactly (bf16)
-    materialize_decoder_act = True   # BatchNorm + ReLU of the first decoder layers' inputs as a pass of its own (see forward)
-    materialize_max_hin = 4          # ... for the layers whose input map is at most this large
+    # stride-2 1x1 shortcuts: the data gradient is written / read at the even positions only, and (bf16, not deterministic) ...
+    compact_shortcut_grad = True     # ... as a dense 1x1 product over the stride-2 grid, stored compactly
+    materialize_max_hin = 4          # BatchNorm + ReLU of a decoder layer's input as a pass of its own up to this map size (see forward)
     light_fork = True                # fork events without the system-scope fence (sv_stream_fork)
     fork_every = 1                   # weight gradients per side-stream fork
     # sv_bwd3x3 (ABI 7 / 8): data gradient + weight gradient of a 32 -> 32 (64 -> 64) channel body convolution in ONE launch that reads every
@@ -600,123 +548,9 @@ class Engine:
     # trace, round 6).  248 = 31 per XCD leaves every XCD one CU for the neighbours.
     fused_blocks = 248
     flag_fork = True                 # paired launches: the data gradient's start signal forks the side stream (no event)
-    _fused_since_fork = False        # an sv_bwd3x3 launch has been issued since the last fork of the side stream
+    _flag_forks_verified = False     # (process-wide) the first backward that forked by flag has been checked with a synchronisation
     event_fork_after_fused = True    # (A/B switch: bench.py --event-fork-after-fused 0)
-    _start_signal = None
-    _pending_wgrads = ()
     fold_bn = True                   # BatchNorm finalisation folded into the consuming sv_igemm launch (sv_igemm_args::fold_*)
-
-    def _side(self):
-        """side stream paired with the current stream"""
-        pool = getattr(self, "_side_streams", None)
-        if pool is None:
-            pool = self._side_streams = {}
-        cur = torch.cuda.current_stream()
-        s = pool.get(cur.cuda_stream)
-        if s is None:
-            s = pool[cur.cuda_stream] = torch.cuda.Stream()
-        return cur, s
-
-    def _wgrad_async(self, g, x, pro, dy, dw_ptr, tag=None, groups=1, budget=0, then=None):
-        """Enqueue the weight gradient behind everything issued so far, on the side stream: the dgrad -> BN-apply
-        chain continues on the main stream without waiting for it (joined at the end of backward).
-        `then`: a callable that issues the main-stream launch paired with this weight gradient (the layer's data gradient).
-        It is issued FIRST, so that the main stream, the critical path, never waits for the host to finish the side stream's
-        bookkeeping (tools/step_timeline.py showed ~8 us of idle main stream per pair), and it carries the fork: its first
-        block stores a sequence number the side stream waits for (sv_igemm_args::start_flag, sv_stream_wait_flag) -- no event
-        in the main stream's queue.  Without a `then` (or where dispatch is serialised: profilers) the fork is an event of the
-        library's pool.  Either way the weight gradient depends only on what preceded the pair."""
-        # (not under hipGraph capture: a captured step replays a hundred cross-stream edges slower than one stream --
-        #  11.6 against 11.05 ms, measured -- and tensors freed during capture would need to outlive the side stream)
-        if not self.wgrad_side_stream or self.prof_tags is not None or torch.cuda.is_current_stream_capturing():
-            self._wgrad(g, x, pro, dy, dw_ptr, tag, groups, budget)
-            return then() if then is not None else None
-        cur, side = self._side()
-        # `fork_every` weight gradients share one fork: every fork is a marker in the main stream's queue that costs it ~6 us of
-        # idle time in front of the next kernel (tools/probes/step_list.py: a gap before every data gradient)
-        self._pending_wgrads.append((g, x, pro, dy, dw_ptr, tag, groups, budget))
-        if len(self._pending_wgrads) < self.fork_every:
-            return then() if then is not None else None
-        # (the first pair behind fused-backward launches forks by event: the host runs ahead, the side stream's wait_flag_kernel for
-        #  this pair would start as soon as the side stream is idle and spin on a CU THROUGH the fused launches in between -- 825 us in
-        #  the trace -- and a fused launch whose waves fill the SIMDs' register files cannot share a CU with it: the workgroups the
-        #  dispatcher had dealt to that CU's shader engine waited for a second round, 137 -> 236 us per launch of the residual form)
-        after_fused, self._fused_since_fork = self._fused_since_fork and self.event_fork_after_fused, False
-        if self.flag_fork and not after_fused and not _dispatch_serialised() and then is not None and len(self._pending_wgrads) == 1:
-            # device-side fork: the paired main-stream launch (`then`, an sv_igemm) announces its own START through a flag word
-            # (sv_igemm_args::start_flag) -- everything this weight gradient depends on has completed by then -- and the side
-            # stream waits for the flag: no event, no marker in the main stream's queue
-            flag, value = C.c_void_p(), C.c_uint32()
-            L.call("sv_stream_flag_next", _vp(cur.cuda_stream), C.byref(flag), C.byref(value))
-            self._start_signal = (flag.value, value.value)
-            try:
-                out = then()
-            finally:
-                armed, self._start_signal = self._start_signal, None
-            if armed is None:          # consumed by the launch
-                L.call("sv_stream_wait_flag", _vp(side.cuda_stream), flag, value)
-                return self._issue_pending(cur, side, out)
-            # (`then` launched nothing that could carry the signal: the ordinary fork, behind it)
-            L.call("sv_stream_fork", _vp(cur.cuda_stream), _vp(side.cuda_stream), int(self.light_fork))
-            return self._issue_pending(cur, side, out)
-        return self._flush_wgrads(cur, side, then)
-
-    def _flush_wgrads(self, cur, side, then=None):
-        """Fork the side stream off the main stream here and issue the pending weight gradients on it.  The fork is an event
-        of the library's pool WITHOUT the system-scope fence of an ordinary event (sv_stream_fork): both streams are on this
-        device."""
-        L.call("sv_stream_fork", _vp(cur.cuda_stream), _vp(side.cuda_stream), int(self.light_fork))
-        out = then() if then is not None else None
-        return self._issue_pending(cur, side, out)
-
-    def _issue_pending(self, cur, side, out=None):
-        with torch.cuda.stream(side):
-            for (g, x, pro, dy, dw_ptr, tag, groups, budget) in self._pending_wgrads:
-                self._wgrad(g, x, pro, dy, dw_ptr, tag, groups, budget)
-        # the operands stay referenced until the streams are joined at the end of backward (no record_stream bookkeeping
-        # per tensor: two allocator calls per weight gradient on the host's critical path)
-        keep = self._side_keep.setdefault(cur.cuda_stream, [])
-        for w in self._pending_wgrads:
-            keep.append((w[1], w[3]))
-        self._pending_wgrads = []
-        return out
-
-    _flag_forks_verified = False     # the first backward that forked by flag has been checked with a synchronisation
-
-    def _join_side(self):
-        if self.wgrad_side_stream and self.prof_tags is None and not torch.cuda.is_current_stream_capturing():
-            cur, side = self._side()
-            if self._pending_wgrads:
-                self._flush_wgrads(cur, side)
-            cur.wait_stream(side)
-            try:
-                if self.flag_fork and not _dispatch_serialised():
-                    # fail closed (sv_stream_wait_flag): the sticky time-out counter is host-mapped, the check is a memory read.  The
-                    # environment sniffing of _dispatch_serialised() cannot know every serialising tool, so the FIRST flag-forked
-                    # backward of an engine is verified with one synchronisation.  A wait that gave up THERE is recoverable: nothing
-                    # has consumed this backward's gradients yet (the optimizer step and the all-reduce come after it), so the engine
-                    # switches to event forks for good, clears the counter and reports THIS step invalid -- a caller that drops it
-                    # (zero_grad, next batch) continues on valid steps.
-                    if not self._flag_forks_verified:
-                        torch.cuda.synchronize()
-                        Engine._flag_forks_verified = True
-                        n = L.lib().sv_flag_timeouts()
-                        if n:
-                            Engine.flag_fork = False
-                            self.flag_fork = False
-                            L.call("sv_flag_timeouts_reset")
-                            raise L.ShotVaeHipError(
-                                "%d side-stream wait(s) for a data gradient's start signal timed out in the first backward of this "
-                                "engine (kernel dispatch is serialised: profiler, debugger): the gradients of THIS backward are invalid "
-                                "-- drop the step (zero_grad) -- and nothing has consumed them yet.  The engine now forks by events "
-                                "(Engine.flag_fork = False); the following steps are valid." % n)
-                    # a LATER time-out is seen by this memory read only once the waiting kernel has run -- possibly a step late, after
-                    # sv_sgd / the all-reduce applied the corrupted gradients: that one is fatal (check_flag_timeouts says so)
-                    L.check_flag_timeouts("Engine.backward")
-            finally:
-                # the side stream's operands may be released now (also when the check raises): the main stream, on which the
-                # allocator will hand their memory out again, is ordered behind everything the side stream did
-                self._side_keep.pop(cur.cuda_stream, None)
 
     def _wgrad(self, g, x, pro, dy, dw_ptr, tag=None, groups=1, budget=0):
         if tag:
@@ -725,9 +559,19 @@ class Engine:
         a.x, a.dy, a.dw = x.data_ptr(), dy.data_ptr(), dw_ptr
         if pro is not None:
             a.pro_scale, a.pro_shift, a.pro_slope = pro[0], pro[1], pro[2]
-        a.splits, a.use_tr, a.ws, a.ws_elems = 0, self.use_tr, self._wg_ws().data_ptr(), self._ws_elems
+        a.splits, a.use_tr, a.ws, a.ws_elems = 0, 1, self._wg_ws().data_ptr(), self._ws_elems
         a.groups, a.block_budget = groups, budget          # the budget is an argument of THIS launch, not process state
         L.call("sv_wgrad_ex", C.byref(g), self.code, C.byref(a), self._stream())
+
+    def _conv_backward(self, cv, B, x, pro, dy, dx, ex, tag, groups, budget=0, wgrad_budget=None, dgeom=None, sparse_out=False):
+        """Backward of conv-like layer `cv` as a pair: its weight gradient (input x behind the prologue `pro`) on the side stream,
+        its data gradient dy -> dx (activation-backward epilogue `ex`) on the main stream.  budget: the block budget of both
+        launches (wgrad_budget: the weight gradient's, where it differs); dgeom: the data gradient's geometry if not cv's own."""
+        w = self.packs.data_ptr() + self.packs.element_size() * cv.dgrad_off
+        self._side.submit((cv.geom_fwd(B), x, pro, dy, self.grad.data_ptr() + 4 * cv.master_off, "wgrad:" + tag, groups,
+                           budget if wgrad_budget is None else wgrad_budget),
+                          then=lambda: self._igemm(dgeom or cv.geom_dgrad(B), dy, w, dx, ex=ex, tag="dgrad:" + tag, groups=groups,
+                                                   budget=budget, sparse_out=sparse_out))
 
     def _bwd3x3(self, cv, B, dy, lin2, x, bn_ptrs, slope, out, bsums, replicas, tag, groups, budget=0, res=None):
         """sv_bwd3x3: data gradient (activation-backward epilogue of the BatchNorm in front: bn_ptrs = scale, shift, mean, rstd) and
@@ -758,7 +602,7 @@ class Engine:
         a.bsums, a.replicas, a.groups = bsums, replicas, groups
         a.dw = self.grad.data_ptr() + 4 * cv.master_off
         a.ws, a.ws_elems, a.block_budget = self._wg_ws().data_ptr(), self._ws_elems, budget or self.fused_blocks
-        self._fused_since_fork = True
+        self._side.note_fused()
         L.call("sv_bwd3x3", C.byref(g), self.code, C.byref(a), self._stream())
 
     def _dropout_fwd(self, c1, unit, keys, stats, replicas, groups):
@@ -955,7 +799,7 @@ class Engine:
                 f.h.append(None)
                 continue
             out = torch.empty(gl * B, ho, ho, cv.N, dtype=T, device=dev)
-            if pro is not None and self.materialize_decoder_act and cv.Hin <= self.materialize_max_hin:
+            if pro is not None and cv.Hin <= self.materialize_max_hin:
                 # weight-heavy layers (1x1 ... 4x4 maps, 1024 ... 256 channels): BatchNorm + ReLU once, as a pass over a few
                 # MB, and a prologue-free GEMM (the LDS-DMA loader) -- fused, the transform was redone per channel tile
                 xa = torch.empty_like(x)
@@ -972,7 +816,7 @@ class Engine:
                 #  is the last ConvTranspose of a launch that runs it for the reconstructed groups only: the running statistics
                 #  need the mean / rstd of EVERY group)
                 pro = finalize(p.dec_bns[i], "h%d" % i, B * ho * ho,
-                               fold=not (self.materialize_decoder_act and p.dec_convs[i + 1].Hin <= self.materialize_max_hin) and (i < 4 or Gd == G))
+                               fold=p.dec_convs[i + 1].Hin > self.materialize_max_hin and (i < 4 or Gd == G))
                 f.dpro.append(pro[:3])
                 x = out
 
@@ -1068,7 +912,6 @@ class Engine:
         if x16 is None:
             image = image.contiguous().float()
         pbase = self.param.data_ptr()
-        pk, es = self.packs.data_ptr(), self.packs.element_size()
         fs = self._fwd_scratch(B, G, training, dev)
         finalize, sptr, stats, bnbuf = fs.finalize, fs.sptr, fs.stats, fs.bnbuf
 
@@ -1250,7 +1093,7 @@ class Engine:
         n = p.Lpad
         for i, cv in enumerate(p.dec_convs):
             n += cv.Hout * cv.Hout * cv.N
-            if i > 0 and self.materialize_decoder_act and cv.Hin <= self.materialize_max_hin:
+            if i > 0 and cv.Hin <= self.materialize_max_hin:
                 n += cv.Hin * cv.Hin * cv.Cin
         return n * es
 
@@ -1406,18 +1249,13 @@ class Engine:
         try:
             backward_fn(*args)
         except BaseException:
-            # the operands kept alive for the side stream must not survive a failed backward into the next step
-            if torch.cuda.is_available():
-                torch.cuda.synchronize()
-            self._side_keep.clear()
-            self._pending_wgrads = []
+            self._side.abort()
             raise
 
     def _bwd_scratch(self, f):
         """The scratch of the backward of forward `f` and the BatchNorm-backward helpers over it, shared by the encoder
         (_encoder_backward) and the tail in front of it: .bs_off / .bs_rep (per BatchNorm: its (sum g, sum g * xhat) accumulator and
         replica count), .bnp(b), .ex_of(b, raw), .bn_apply(...), .bn_fold(b, count), .bn_affine(b, count)."""
-        p = self.plan
         B, G = f.B, f.G
         dev = f.feat.device
         st = self._stream()
@@ -1511,8 +1349,6 @@ class Engine:
         dev = f.feat.device
         st = self._stream()
         pbase, gbase = self.param.data_ptr(), self.grad.data_ptr()
-        pk, es = self.packs.data_ptr(), self.packs.element_size()
-        nb = f.bnbuf.data_ptr()
         bx = self._bwd_scratch(f)
         ex_of, bn_apply = bx.ex_of, bx.bn_apply
 
@@ -1545,19 +1381,14 @@ class Engine:
                 # (where the forward materialised BatchNorm + ReLU of this layer's input, the weight gradient reads that)
                 wx, wpro = (f.ha[i][:Bd], None) if i in f.ha else (hin, f.dpro[i - 1])
                 # (the last layer's data gradient is a whole-CU kernel of dconv.hip: with a budget it leaves CUs to the weight gradient
-                #  beside it -- Engine.pair_blocks_strided)
+                #  beside it -- Engine.pair_blocks_strided; the weight gradient itself runs without one.  Unlike WgradSideStream.enabled()
+                #  this condition does not look at hipGraph capture: a captured step keeps the budget, kept as it is)
                 dbud = self.pair_blocks_strided if (i == 5 and self.wgrad_side_stream and self.prof_tags is None) else 0
-                self._wgrad_async(cv.geom_fwd(B), wx, wpro, D, gbase + 4 * cv.master_off, tag="wgrad:dec%d" % i,
-                                  groups=Gd, then=lambda: self._igemm(cv.geom_dgrad(B), D, pk + es * cv.dgrad_off, g,
-                                                                      ex=ex_of(b, hin, Gd), tag="dgrad:dec%d" % i, groups=Gd,
-                                                                      budget=dbud))
+                self._conv_backward(cv, B, wx, wpro, D, g, ex_of(b, hin, Gd), "dec%d" % i, Gd, budget=dbud, wgrad_budget=0)
                 D = bn_apply(hin, [(g, b)], None, hin.numel() // hin.shape[-1] // Gd, Gd)
-            cv = p.dec_convs[0]
             lat4 = f.latent.view(Bt, 1, 1, p.Lpad)[:Bd]
             dlat = torch.empty(Bd, 1, 1, p.Lpad, dtype=T, device=dev)
-            self._wgrad_async(cv.geom_fwd(B), lat4, None, D, gbase + 4 * cv.master_off, tag="wgrad:dec0", groups=Gd,
-                              then=lambda: self._igemm(cv.geom_dgrad(B), D, pk + es * cv.dgrad_off, dlat, tag="dgrad:dec0",
-                                                       groups=Gd))
+            self._conv_backward(p.dec_convs[0], B, lat4, None, D, dlat, None, "dec0", Gd)
             # ---- sampler (the latent's gradient reaches mu / log_sigma / log_alpha) -------------------------------
             dl2 = dlat.view(Bd, p.Lpad)
             fused = self.fused_glue and Gd <= L.MAX_SAMPLE_GROUPS
@@ -1577,8 +1408,7 @@ class Engine:
         # (finish() falls back to the single all-reduce if no decoder backward follows).
         if self.bucket_hook is not None and Gd > 0:
             hook, self.bucket_hook = self.bucket_hook, None
-            if self._pending_wgrads:       # (fork_every > 1: the decoder's last weight gradients must be ISSUED before the hook)
-                self._flush_wgrads(*self._side())
+            self._side.flush()             # (fork_every > 1: the decoder's last weight gradients must be ISSUED before the hook)
             hook()
         # ---- heads + pool ---------------------------------------------------------------------------------------
         dfeat = torch.empty(Bt, p.cfeat, dtype=torch.float32, device=dev)
@@ -1598,7 +1428,6 @@ class Engine:
         dev = dfeat.device
         st = self._stream()
         pbase, gbase = self.param.data_ptr(), self.grad.data_ptr()
-        pk, es = self.packs.data_ptr(), self.packs.element_size()
         det, bs_off, bs_rep = bx.det, bx.bs_off, bx.bs_rep
         bnp, ex_of, bn_apply, bn_fold, bn_affine = bx.bnp, bx.ex_of, bx.bn_apply, bx.bn_fold, bx.bn_affine
         tl = f.t[-1]
@@ -1617,8 +1446,7 @@ class Engine:
             c = un["cout"]
             # paired launches: the weight gradient (side stream) and the data gradient (main stream) of a body convolution
             # each get `pair` persistent blocks as a per-launch argument (sv_igemm_args / sv_wgrad_args::block_budget)
-            pair = self.pair_blocks if ((self.wgrad_side_stream and self.prof_tags is None and
-                                         not torch.cuda.is_current_stream_capturing()) or self.prof_paired) else 0
+            pair = self.pair_blocks if (self._side.enabled() or self.prof_paired) else 0
             pair = min(pair, L.lib().sv_get_option(L.OPT_PERSISTENT_BLOCKS))
             same = un["stride"] == 1 and un["cin"] == c
             cnt2 = c1.numel() // c // G
@@ -1645,11 +1473,7 @@ class Engine:
                 self._bwd3x3(un["conv2"], B, D, None, c1, bnp(un["bn2"]), un["bn2"].slope, g2, bs_off[un["bn2"].index],
                              bs_rep[un["bn2"].index], "bwd:conv3x3_%dx%d_s1" % (c, c), G)
             else:
-                self._wgrad_async(un["conv2"].geom_fwd(B), c1, pro2, D, gbase + 4 * un["conv2"].master_off,
-                                  tag="wgrad:conv3x3_%dx%d_s1" % (c, c), groups=G, budget=pair,
-                                  then=lambda: self._igemm(un["conv2"].geom_dgrad(B), D, pk + es * un["conv2"].dgrad_off, g2,
-                                                           ex=ex_of(un["bn2"], c1), tag="dgrad:conv3x3_%dx%d_s1" % (c, c),
-                                                           groups=G, budget=pair))
+                self._conv_backward(un["conv2"], B, c1, pro2, D, g2, ex_of(un["bn2"], c1), "conv3x3_%dx%d_s1" % (c, c), G, budget=pair)
             # (the in-situ table times every launch ALONE: the strided pair's budget only makes sense beside its weight gradient)
             pair1 = pair if same else (min(pair, self.pair_blocks_strided) if self.prof_tags is None else 0)
             cnt = tin.numel() // tin.shape[-1] // G
@@ -1673,13 +1497,9 @@ class Engine:
                 dc1 = None
             else:
                 dc1 = bn_apply(c1, [(g2, un["bn2"])], None, cnt2, drop_unit=drop_unit)
-                self._wgrad_async(un["conv1"].geom_fwd(B), tin, pro1, dc1, gbase + 4 * un["conv1"].master_off,
-                                  tag="wgrad:" + tag1, groups=G, budget=pair1,
-                                  then=lambda: self._igemm(un["conv1"].geom_dgrad(B), dc1, pk + es * un["conv1"].dgrad_off, g1,
-                                                           ex=ex_of(un["bn1"], tin), tag="dgrad:" + tag1, groups=G, budget=pair1))
+                self._conv_backward(un["conv1"], B, tin, pro1, dc1, g1, ex_of(un["bn1"], tin), tag1, G, budget=pair1)
             del g2
             del dc1
-            cnt = tin.numel() // tin.shape[-1] // G
             if "convi" in un and un["stride"] == 2 and self.compact_shortcut_grad and self.code == L.SV_BF16 and not det:
                 # the stride-2 shortcut's data gradient as a DENSE 1x1 product over the stride-2 grid: the raw tensor's even
                 # positions are gathered once (sv_gather_even), the gradient is stored compactly and sv_bn_bwd_apply reads it
@@ -1690,22 +1510,16 @@ class Engine:
                        _vp(tin_c.data_ptr()), st)
                 gi_ = torch.empty_like(tin_c)
                 gdense = _GEOM.conv_like(B, Hq, Hq, c, un["cin"], 1, 1, 0)
-                self._wgrad_async(un["convi"].geom_fwd(B), tin, proi, D, gbase + 4 * un["convi"].master_off,
-                                  tag="wgrad:conv1x1_%dx%d" % (un["cin"], c), groups=G,
-                                  then=lambda: self._igemm(gdense, D, pk + es * un["convi"].dgrad_off, gi_,
-                                                           ex=ex_of(un["bni"], tin_c),
-                                                           tag="dgrad:conv1x1_%dx%d" % (un["cin"], c), groups=G))
+                self._conv_backward(un["convi"], B, tin, proi, D, gi_, ex_of(un["bni"], tin_c), "conv1x1_%dx%d" % (un["cin"], c), G,
+                                    dgeom=gdense)
                 D = bn_apply(tin, [(g1, un["bn1"]), (gi_, un["bni"])], None, cnt, sparse=(1,), compact=True)
                 del tin_c
             elif "convi" in un:
                 gi_ = torch.empty_like(tin)
                 # a stride-2 shortcut's data gradient is zero at three of four positions: those are neither written nor read
-                sp = un["stride"] == 2 and self.sparse_shortcut_grad
-                self._wgrad_async(un["convi"].geom_fwd(B), tin, proi, D, gbase + 4 * un["convi"].master_off,
-                                  tag="wgrad:conv1x1_%dx%d" % (un["cin"], c), groups=G,
-                                  then=lambda: self._igemm(un["convi"].geom_dgrad(B), D, pk + es * un["convi"].dgrad_off, gi_,
-                                                           ex=ex_of(un["bni"], tin), sparse_out=sp,
-                                                           tag="dgrad:conv1x1_%dx%d" % (un["cin"], c), groups=G))
+                sp = un["stride"] == 2
+                self._conv_backward(un["convi"], B, tin, proi, D, gi_, ex_of(un["bni"], tin), "conv1x1_%dx%d" % (un["cin"], c), G,
+                                    sparse_out=sp)
                 D = bn_apply(tin, [(g1, un["bn1"]), (gi_, un["bni"])], None, cnt, sparse=(1,) if sp else ())
             elif fb >= 2 and same and i > 0 and p.units[i - 1]["cout"] == c:
                 # the boundary pass (norm1's backward + the skip connection) is left to conv2 of the unit in front (see above)
@@ -1715,6 +1529,6 @@ class Engine:
                 D = bn_apply(tin, [(g1, un["bn1"])], D, cnt)
         assert deferred is None
         # ---- stem: weight + bias gradients (the image needs none) ---------------------------------
-        self._wgrad_async(p.stem.geom_fwd(B), f.x16, None, D, gbase + 4 * p.stem.master_off, tag="wgrad:stem", groups=G)
+        self._side.submit((p.stem.geom_fwd(B), f.x16, None, D, gbase + 4 * p.stem.master_off, "wgrad:stem", G))
         L.call("sv_colsum", self.code, _vp(D.data_ptr()), D.numel() // p.stem_n, p.stem_n, p.stem_n, _vp(gbase + 4 * p.stem_bias_off), st)
-        self._join_side()
+        self._side.join()

@@ -84,3 +84,41 @@ def with_batch(g, B):
     h = SvGeom.from_buffer_copy(g)
     h.B = B
     return h
+
+
+class ConvSpec:
+    """One conv-like layer: kind 'conv' (Conv2d, Linear as a k=1 conv) or 'convT' (ConvTranspose2d, the k=1 ConvTranspose GEMM); the offsets are its owner's."""
+
+    def __init__(self, key, kind, k, stride, pad, cin, n, hin, cin_real=None, n_real=None):
+        self.key, self.kind, self.k, self.stride, self.pad = key, kind, k, stride, pad
+        self.Cin, self.N, self.Hin = cin, n, hin
+        self.cin_real, self.n_real = cin_real or cin, n_real or n
+        self.T = k * k
+        self.master_off = self.fwd_off = self.dgrad_off = None
+        self._g = {}
+
+    @property
+    def Hout(self):
+        return (self.Hin + 2 * self.pad - self.k) // self.stride + 1 if self.kind == "conv" else self.Hin * self.stride
+
+    def geom_fwd(self, B):
+        g = self._g.get(("f", B))
+        if g is None:
+            f = conv_like if self.kind == "conv" else convT_like
+            g = self._g[("f", B)] = f(B, self.Hin, self.Hin, self.Cin, self.N, self.k, self.stride, self.pad)
+        return g
+
+    def geom_dgrad(self, B):
+        """input = gradient w.r.t. this layer's output, output = gradient w.r.t. its input."""
+        g = self._g.get(("d", B))
+        if g is None:
+            f = convT_like if self.kind == "conv" else conv_like
+            g = self._g[("d", B)] = f(B, self.Hout, self.Hout, self.N, self.Cin, self.k, self.stride, self.pad)
+        return g
+
+    def torch_view(self, master):
+        """The reference-shaped (OIHW for Conv2d, IOHW for ConvTranspose2d) strided view."""
+        m = master[self.master_off: self.master_off + self.N * self.T * self.Cin].view(self.N, self.k, self.k, self.Cin)
+        if self.kind == "conv":
+            return m.permute(0, 3, 1, 2)[: self.n_real, : self.cin_real]
+        return m.permute(3, 0, 1, 2)[: self.cin_real, : self.n_real]

@@ -277,37 +277,6 @@ class _WeightPlan:
         self._fresh = []
 
 
-class _Layer:
-    """Static description of one conv-like layer: kind 'conv' (Conv2d / Linear-as-conv) or 'convT'."""
-
-    def __init__(self, kind, k, stride, pad, cin, n, hin, cin_real=None, n_real=None):
-        self.kind, self.k, self.stride, self.pad = kind, k, stride, pad
-        self.Cin, self.N, self.Hin = cin, n, hin
-        self.cin_real, self.n_real = cin_real or cin, n_real or n
-        self.T = k * k
-        self._g = {}
-
-    @property
-    def Hout(self):
-        if self.kind == "conv":
-            return (self.Hin + 2 * self.pad - self.k) // self.stride + 1
-        return self.Hin * self.stride
-
-    def geom_fwd(self, B):
-        g = self._g.get(("f", B))
-        if g is None:
-            f = G.conv_like if self.kind == "conv" else G.convT_like
-            g = self._g[("f", B)] = f(B, self.Hin, self.Hin, self.Cin, self.N, self.k, self.stride, self.pad)
-        return g
-
-    def geom_dgrad(self, B):
-        g = self._g.get(("d", B))
-        if g is None:
-            f = G.convT_like if self.kind == "conv" else G.conv_like
-            g = self._g[("d", B)] = f(B, self.Hout, self.Hout, self.N, self.Cin, self.k, self.stride, self.pad)
-        return g
-
-
 class _ConvLikeFn(torch.autograd.Function):
     """out = conv_like(ReLU?(x)) + bias through sv_igemm on the pre-packed weights of the model's _WeightPlan; backward =
     sv_igemm (data gradient with the ReLU backward as its epilogue), sv_wgrad and sv_colsum into the plan's gradient scratch.
@@ -500,13 +469,13 @@ class SmoothVAE(nn.Module):
                                              nn.ConvTranspose2d(d1, d2, 4, 2, 1), nn.ReLU(),
                                              nn.ConvTranspose2d(d2, ch, 4, 2, 1), nn.Tanh())
         NH = 2 * self.latent_cont_dim + self.latent_disc_dim
-        self._L = dict(
-            c1=_Layer("conv", 4, 2, 1, 16, w1, 32, cin_real=ch), c2=_Layer("conv", 4, 2, 1, w1, w2, 16),
-            c3=_Layer("conv", 4, 2, 1, w2, w3, 8), f1=_Layer("conv", 1, 1, 0, w3 * 16, h, 1),
-            heads=_Layer("conv", 1, 1, 0, h, _pad16(NH), 1, n_real=NH),
-            g1=_Layer("conv", 1, 1, 0, _pad16(lat), h, 1, cin_real=lat), g2=_Layer("conv", 1, 1, 0, h, w3 * 16, 1),
-            t1=_Layer("convT", 4, 2, 1, w3, d1, 4), t2=_Layer("convT", 4, 2, 1, d1, d2, 8),
-            t3=_Layer("convT", 4, 2, 1, d2, 16, 16, n_real=ch))
+        self._L = {l.key: l for l in (
+            G.ConvSpec("c1", "conv", 4, 2, 1, 16, w1, 32, cin_real=ch), G.ConvSpec("c2", "conv", 4, 2, 1, w1, w2, 16),
+            G.ConvSpec("c3", "conv", 4, 2, 1, w2, w3, 8), G.ConvSpec("f1", "conv", 1, 1, 0, w3 * 16, h, 1),
+            G.ConvSpec("heads", "conv", 1, 1, 0, h, _pad16(NH), 1, n_real=NH),
+            G.ConvSpec("g1", "conv", 1, 1, 0, _pad16(lat), h, 1, cin_real=lat), G.ConvSpec("g2", "conv", 1, 1, 0, h, w3 * 16, 1),
+            G.ConvSpec("t1", "convT", 4, 2, 1, w3, d1, 4), G.ConvSpec("t2", "convT", 4, 2, 1, d1, d2, 8),
+            G.ConvSpec("t3", "convT", 4, 2, 1, d2, 16, 16, n_real=ch))}
         self._tdt = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
         self._plans = {}
         self._tokens = {}

@@ -1635,7 +1635,7 @@ def test_start_signal_forks_a_second_stream(case):
 
 def test_flag_fork_fails_closed_on_a_timeout():
     """A side-stream wait whose signal never comes gives up after ~3 s -- and must not pass silently: the sticky host-mapped
-    counter makes the next check raise (Engine._join_side, FlatSGD.step, dp's all-reduce all call L.check_flag_timeouts),
+    counter makes the next check raise (WgradSideStream.join, FlatSGD.step, dp's all-reduce all call L.check_flag_timeouts),
     without a copy or a synchronisation of its own."""
     import shot_vae_amd as S
     d = dev()
@@ -1693,7 +1693,7 @@ def test_flag_fork_timeout_in_the_first_backward_is_recoverable():
         with pytest.raises(L.ShotVaeHipError, match="drop the step"):
             S.train_step_grouped(model, elbo, cls, opt, il, ll, iu, S.schedule(10))
         assert L.lib().sv_flag_timeouts() == 0 and model._engine.flag_fork is False and Engine._flag_forks_verified
-        assert not model._engine._side_keep
+        assert not model._engine._side.keep
         opt.zero_grad()
         before = model._engine.param.clone()
         ls, lu = S.train_step_grouped(model, elbo, cls, opt, il, ll, iu, S.schedule(10))      # event forks: a valid step
