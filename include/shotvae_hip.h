@@ -551,6 +551,31 @@ int sv_aggpost_dims(const float* z, int Q, const float* g_mu, const float* g_ls,
                     double* s, int P, int init, void* stream);
 int sv_aggpost_finish(const double* m, const double* s, int P, int64_t R, int64_t count, float* out, void* stream);
 
+/* ---- membership counts of k-th-neighbour balls: precision / recall, density / coverage (manifold.hip) -----------
+ * Added under ABI 8: new symbols only.  mu and ls are fp32 [rows][D] with row stride D; ls is LOG SIGMA, as in the sections above.
+ *
+ * sv_ball_scan: gallery row j of this call -- global index col0 + j -- carries a ball of radius g_r[j] (fp32 [N], in the metric's own,
+ *   squared, units: a value of sv_knn_scan's list).  v(i, j) is THE VALUE sv_pairdist GIVES THE PAIR, bit for bit (direct differences,
+ *   16 dimensions in fp32 with explicit fmaf in index order, the 16-blocks in double in index order, rounded once to fp32).  Query i
+ *   is inside ball j when
+ *       v(i, j) is finite,   v(i, j) <= g_r[j],   and   col0 + j != self0 + i   (self0 = -1: no exclusion)
+ *   so a NaN radius or value contains nothing, a radius of +inf every finite pair, a negative radius nothing, a radius of 0 the
+ *   coincident rows only.  Then
+ *       q_count[i] += the number of balls of the call that query i is inside        (int64 [Q])
+ *       g_count[j] += the number of queries of the call inside ball j               (int64 [N])
+ *   Either may be NULL, not both.  Both are ADDED TO (sv_knn_vote's rule for its counters): the caller zeroes them.  SV_DIST_EUCLID and
+ *   SV_DIST_W2 only: KL is not symmetric (a k-th-neighbour radius has no single meaning under it) and the cosine is a similarity; both
+ *   are refused.  The grid is ceil(Q / 64) x P blocks, gallery tile t (64 rows) of the call goes to block t mod P, 1 <= P <= 64.  The
+ *   counts are integers of the pair set: a gallery cut into calls (col0, shifted g_r / g_count), a query set cut into calls (shifted
+ *   q_count, self0 + the cut) and any P give identical results.  Counts meet in registers / LDS inside a block, which issues at most
+ *   one integer atomic per row at its end and one per touched column and tile; no float atomics.
+ *
+ * Validated before any HIP call (SV_E_ARG / SV_E_SHAPE, nothing launched): an unknown, KL or cosine metric; NULL q_mu, g_mu or g_r;
+ * a NULL ls under W2; both counters NULL; Q, N or D < 1; a negative col0; self0 < -1; P outside [1, 64]; col0 + N or self0 + Q beyond
+ * the index (SV_E_SHAPE).  Takes a stream and allocates nothing: capturable.                                                        */
+int sv_ball_scan(int metric, const float* q_mu, const float* q_ls, int Q, const float* g_mu, const float* g_ls, const float* g_r, int N,
+                 int D, int64_t col0, int64_t self0, int P, int64_t* q_count, int64_t* g_count, void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

@@ -17,4 +17,5 @@ from .smooth import (SmoothVAE, svhn_VAE, mnist_VAE, SmoothELBOLoss, smooth_trai
 from .neighbors import (LatentIndex, encode_posterior, pairwise_distance, pairwise_norm_kl_dist_gpu,      # noqa: F401
                         pairwise_square_euclidean_gpu, pairwise_norm_wasserstein_dist_gpu, calculate_mean_dist_pairwise)
 from .aggregate import AggregatePosterior, evaluate_aggregate      # noqa: F401
+from .quality import (Manifold, manifold_metrics, FeatureMoments, frechet_distance, evaluate_generation)      # noqa: F401
 from .trace import StepLogger, step_range, enable_ranges     # noqa: F401
