@@ -576,6 +576,52 @@ int sv_aggpost_finish(const double* m, const double* s, int P, int64_t R, int64_
 int sv_ball_scan(int metric, const float* q_mu, const float* q_ls, int Q, const float* g_mu, const float* g_ls, const float* g_r, int N,
                  int D, int64_t col0, int64_t self0, int P, int64_t* q_count, int64_t* g_count, void* stream);
 
+/* ---- latent-space clustering: fused k-means and the contingency table of two partitions (cluster.hip) -----------
+ * Added under ABI 8: new symbols only.  Rows x are fp32 [N][D] with row stride D, centroids c fp32 [K][D].  Squared Euclid only: the W2
+ * distance of diagonal Gaussians is the squared Euclid distance of the concatenated rows [mu, exp(ls)] -- cluster those.
+ *
+ * sv_kmeans_assign: v(i, j) is THE VALUE sv_pairdist GIVES THE PAIR (x_i, c_j) UNDER SV_DIST_EUCLID, bit for bit (direct differences,
+ *   16 dimensions in fp32 with explicit fmaf in index order, the 16-blocks in double in index order, rounded once to fp32).
+ *       assign[i] = the smallest j that attains the minimum over the FINITE v(i, .); -1 when no value is finite (a NaN or infinite row,
+ *                   every centroid NaN)                                                                            (int64 [N])
+ *       dist[i]   = that minimum; +inf when assign[i] is -1                                                       (fp32 [N], may be NULL)
+ *   The [N][K] matrix is never stored; K is tiled like sv_knn_scan's gallery: any K >= 1.  A row's result does not depend on the rows
+ *   around it: rows cut into calls give the same bits.
+ *
+ * sv_kmeans_accum: the N rows of the call are dealt to the P partial states in tiles of 64 rows (tile t to state t mod P).  A state is
+ *       sums    double [P][K][D]    sums[p][k][d] += (double)x[i][d] for the state's rows with assign[i] == k, IN ROW ORDER, one double
+ *                                   add per (row, dimension)
+ *       counts  int64  [P][K]       the number of those rows
+ *       inertia double [P]          += (double)dist[i] over the state's rows with assign[i] in [0, K), in row order (may be NULL; needs dist)
+ *   A row with assign[i] outside [0, K) is skipped.  init != 0 zeroes the states first (the caller need not initialise them); with
+ *   init == 0 they continue as an earlier call left them.  Hence: a repeated call gives the same bits; with P = 1 the rows may be cut
+ *   into calls at any multiple of 64, with P > 1 at any multiple of 64 P, and the states hold the bits of the one call.  No atomics.
+ *   1 <= K <= 1024 (a block keeps [K][slice] doubles in LDS, slice = 64 dimensions for K <= 256, 32 for K <= 512, 16 beyond);
+ *   1 <= P <= 64.
+ *
+ * sv_kmeans_finish: with n_k = sum_p counts[p][k] and s_kd = sum_p sums[p][k][d], both in index order (s in double):
+ *       c_new[k][d] = (float)(s_kd / (double)n_k)     n_k > 0;      = c_old[k][d]     n_k == 0: an empty cluster KEEPS its centroid
+ *       count[k]    = n_k                                                                                          (int64 [K])
+ *       stats[0]    = (float) sum_k ( sum_d ((double)c_new[k][d] - (double)c_old[k][d])^2 )    in double; the inner sums over d in index
+ *                     order, then the K inner sums in index order; rounded once
+ *       stats[1]    = (float) sum_p inertia[p]    in double, index order; 0 when inertia is NULL                  (fp32 [2])
+ *   c_new may alias c_old.  Between its two launches count[] carries the inner sums of stats[0]; it holds n_k when the call's work is done.
+ *
+ * sv_contingency: table[a[i]][b[i]] += 1 (int64 [Ka][Kb]) for the rows with a[i] in [0, Ka) and b[i] in [0, Kb); counts[0] += the number
+ *   of such rows, counts[1] += N (int64 [2]).  a, b: int64 [N].  Everything ACCUMULATES (the caller zeroes), under sv_knn_vote's counting
+ *   rules: integer atomics only, a block counts its rows privately and issues at most one atomic per touched cell at its end.
+ *   Ka * Kb <= 2^20.
+ *
+ * Validated before any HIP call (SV_E_ARG / SV_E_SHAPE, nothing launched): a null pointer (dist and inertia excepted; an inertia
+ * without dist), a size < 1, K > 1024 for the accumulation, P outside [1, 64], Ka * Kb > 2^20 (SV_E_SHAPE).  No float atomics anywhere;
+ * each takes a stream and allocates nothing: capturable; a repeated call sequence gives the same bits.                              */
+int sv_kmeans_assign(const float* x, int N, const float* c, int K, int D, int64_t* assign, float* dist, void* stream);
+int sv_kmeans_accum(const float* x, const int64_t* assign, const float* dist, int N, int D, int K, double* sums, int64_t* counts,
+                    double* inertia, int P, int init, void* stream);
+int sv_kmeans_finish(const double* sums, const int64_t* counts, const double* inertia, int P, int K, int D, const float* c_old,
+                     float* c_new, int64_t* count, float* stats, void* stream);
+int sv_contingency(const int64_t* a, const int64_t* b, int N, int Ka, int Kb, int64_t* table, int64_t* counts, void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

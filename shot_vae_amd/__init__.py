@@ -18,4 +18,6 @@ from .neighbors import (LatentIndex, encode_posterior, pairwise_distance, pairwi
                         pairwise_square_euclidean_gpu, pairwise_norm_wasserstein_dist_gpu, calculate_mean_dist_pairwise)
 from .aggregate import AggregatePosterior, evaluate_aggregate      # noqa: F401
 from .quality import (Manifold, manifold_metrics, FeatureMoments, frechet_distance, evaluate_generation)      # noqa: F401
+from .cluster import (KMeans, kmeans_plus_plus, contingency, linear_assignment, partition_metrics,      # noqa: F401
+                      evaluate_clustering)
 from .trace import StepLogger, step_range, enable_ranges     # noqa: F401

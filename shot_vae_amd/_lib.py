@@ -172,6 +172,10 @@ _PROTOS = {
     "sv_aggpost_dims": [P, I, P, P, I, I, I64, I64, P, P, I, I, P],
     "sv_aggpost_finish": [P, P, I, I64, I64, P, P],
     "sv_ball_scan": [I, P, P, I, P, P, P, I, I, I64, I64, I, P, P, P],
+    "sv_kmeans_assign": [P, I, P, I, I, P, P, P],
+    "sv_kmeans_accum": [P, P, P, I, I, I, P, P, P, I, I, P],
+    "sv_kmeans_finish": [P, P, P, I, I, I, P, P, P, P, P],
+    "sv_contingency": [P, P, I, I, I, P, P, P],
     "sv_elbo_fwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P],
     "sv_elbo_bwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P, P, P, P, P],
     "sv_cls_fwd": [P, P, P, I, I, P, P],
