@@ -622,6 +622,72 @@ int sv_kmeans_finish(const double* sums, const int64_t* counts, const double* in
                      float* c_new, int64_t* count, float* stats, void* stream);
 int sv_contingency(const int64_t* a, const int64_t* b, int N, int Ka, int Kb, int64_t* table, int64_t* counts, void* stream);
 
+/* ---- calibration, temperature scaling and rank counts for the class posterior q(y | x) (calib.hip) ---------------
+ * Added under ABI 8: new symbols only.  x is fp32 [N][ldx]; only the first K columns of a row are ever read (ldx >= K).
+ *   kind SV_CAL_LOGIT   u = x          logits or log-probabilities
+ *        SV_CAL_PROB    u = log(x)     probabilities, x >= 0 (a zero is a class of probability 0; a negative entry makes the row NaN)
+ *
+ * sv_calib_rows: with T = *temp (a DEVICE float, read on the device: a captured call follows a refitted temperature; NULL: T = 1),
+ *   z = u / T in fp32 and p = softmax(z):
+ *       pred[i]    = the smallest k that attains max_k z_k                                                       (int64 [N])
+ *       conf[i]    = p[pred]                entropy[i] = -sum_k p_k log p_k,  0 log 0 = 0                        (fp32 [N] each)
+ *       nll[i]     = -log p[label]          brier[i]   = sum_k (p_k - [k == label])^2      for a label[i] in [0, K)
+ *   A row whose K entries hold a NaN or +inf, or nothing but -inf -- or any row when T is not > 0 -- gives pred = -1 and NaN elsewhere.
+ *   A finite row whose label is outside [0, K), or label == NULL, gives NaN for nll and brier only.  Every output pointer is optional;
+ *   one at least must be given; an output that is NULL is not written.  Any K >= 1: a row is taken by min(64, the power of two >= K)
+ *   neighbouring lanes, and up to 256 classes are read once.  A row's result does not depend on the rows around it.
+ *
+ * sv_calib_accum: a row is VALID when pred[i] >= 0 and label[i] is in [0, K).  Its bin is b = #{ i in 1 .. B-1 : edges[i] < conf[i] }
+ *   (edges fp32 [B + 1], NON-DECREASING; only the inner edges are read, compared in fp32: intervals (lo, hi], every value lands in a bin).
+ *       bin_count[b] += 1      bin_correct[b] += (pred == label)                                                 (int64 [B] each)
+ *       counts[0..2] += (valid rows, rows with pred == label among them, N)                                      (int64 [3])
+ *   These are integer adds: exact, they ACCUMULATE (the caller zeroes them; `init` does not touch them).
+ *       sums   double [P][B + 3]    [p][b] += (double)conf[i] for the state's valid rows of bin b; [p][B], [p][B + 1], [p][B + 2] +=
+ *                                   (double)nll[i], brier[i], entropy[i] of the state's valid rows
+ *   under sv_kmeans_accum's partial-state rule: tile t (64 rows) of the call goes to state t mod P; inside a state the rows are added in
+ *   index order, one double add per row and quantity; init != 0 zeroes the states first, otherwise they continue.  nll, brier and entropy
+ *   may be NULL: that total is left untouched (zero after init).  Hence: a repeated call gives the same bits; with P = 1 the rows may be
+ *   cut into calls at any multiple of 64, with P > 1 at any multiple of 64 P.  No float atomic.
+ *
+ * sv_calib_finish: with n_b = bin_count[b], k_b = bin_correct[b], s_b = sum_p sums[p][b] (index order), n = counts[0]; acc_b = k_b / n_b,
+ *   conf_b = s_b / n_b, everything in double and rounded once:
+ *       out[0..7] = counts[1] / n,  (sum_b s_b) / n,  ECE = sum_b n_b / n |acc_b - conf_b|,  MCE = max over n_b > 0 of |acc_b - conf_b|,
+ *                   the means of nll, brier and entropy (sum_p sums[p][B + .] / n),  (float)n                    (fp32 [8])
+ *       diagram   = acc_b, then conf_b; NaN for an empty bin                                                     (fp32 [2][B], may be NULL)
+ *   the sums over b in bin order.  With n == 0 out[0..6] are NaN.
+ *
+ * sv_temp_accum: with beta = *beta (a DEVICE double, 1 / T; used as (float)beta) and p = softmax(beta u) in fp32, per row with a finite
+ *   u (the rule of sv_calib_rows) and a label in [0, K):
+ *       a = E_p[u] - u[label]      v = sum_k p_k (u_k - E_p[u])^2      nll = -log p[label]
+ *   sums double [P][3] += (a, v, nll) and count int64 [P] += 1 under the partial-state rule above (init zeroes both).  The sums of a and v
+ *   are dL/dbeta and d2L/dbeta2 of the summed NLL L(beta), which is convex in beta.
+ *
+ * sv_temp_update: one block.  A, V, L, n = the states merged in index order.  beta_new = beta - A / V clamped to [beta / 4, 4 beta] when
+ *   beta > 0, V > 0 and A, V are finite; beta otherwise.  Writes *beta = beta_new, *temp = (float)(1 / beta_new) -- the pointer
+ *   sv_calib_rows reads -- and stats[0..3] = L / n (at the OLD beta), A / n, beta_new - beta, beta_new (fp32 [4]; NaN means for n == 0).
+ *   A fit of `iters` iterations is 2 iters launches and no host read.
+ *
+ * sv_rank_scan: greater[i] += sum_j w_j [g_j > q_i], equal[i] += sum_j w_j [g_j == q_i] (int64 [Q] each; they ACCUMULATE, the caller
+ *   zeroes them).  q fp32 [Q], g fp32 [N], g_w int64 [N], non-negative (NULL: every weight 1).  IEEE comparisons: a NaN on either side
+ *   counts nowhere, infinities compare as numbers, -0 == 0.  The [Q][N] matrix is never stored; the gallery is staged through LDS in
+ *   chunks of 1024, chunk c by the blocks of grid row c mod P; a block issues one integer atomic per row and count.  Exact, and
+ *   independent of P, of the grid and of any cut of the gallery into calls.  The weights are a MASK: no caller compacts a gallery.
+ *
+ * Validated before any HIP call (nothing launched): a NULL required pointer, a size < 1 (N, K, Q), an unknown kind: SV_E_ARG; ldx < K, B
+ * outside [1, 1024], P outside [1, 64]: SV_E_SHAPE.  Each takes a stream and allocates nothing: capturable.                            */
+enum { SV_CAL_LOGIT = 0, SV_CAL_PROB = 1 };
+int sv_calib_rows(int kind, const float* x, int ldx, int N, int K, const float* temp, const int64_t* label, int64_t* pred, float* conf,
+                  float* nll, float* brier, float* entropy, void* stream);
+int sv_calib_accum(const float* conf, const int64_t* pred, const int64_t* label, const float* nll, const float* brier, const float* entropy,
+                   int N, int K, const float* edges, int B, int64_t* bin_count, int64_t* bin_correct, int64_t* counts, double* sums, int P,
+                   int init, void* stream);
+int sv_calib_finish(const int64_t* bin_count, const int64_t* bin_correct, const int64_t* counts, const double* sums, int P, int B, float* out,
+                    float* diagram, void* stream);
+int sv_temp_accum(int kind, const float* x, int ldx, int N, int K, const int64_t* label, const double* beta, double* sums, int64_t* count,
+                  int P, int init, void* stream);
+int sv_temp_update(const double* sums, const int64_t* count, int P, double* beta, float* temp, float* stats, void* stream);
+int sv_rank_scan(const float* q, int Q, const float* g, const int64_t* g_w, int N, int P, int64_t* greater, int64_t* equal, void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

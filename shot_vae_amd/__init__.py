@@ -20,4 +20,6 @@ from .aggregate import AggregatePosterior, evaluate_aggregate      # noqa: F401
 from .quality import (Manifold, manifold_metrics, FeatureMoments, frechet_distance, evaluate_generation)      # noqa: F401
 from .cluster import (KMeans, kmeans_plus_plus, contingency, linear_assignment, partition_metrics,      # noqa: F401
                       evaluate_clustering)
+from .calibration import (row_stats, Reliability, TemperatureScaler, rank_counts, detection_metrics,      # noqa: F401
+                          selective_metrics, evaluate_calibration, evaluate_detection)
 from .trace import StepLogger, step_range, enable_ranges     # noqa: F401

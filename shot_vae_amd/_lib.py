@@ -16,6 +16,7 @@ SV_F32, SV_BF16 = 0, 1
 ABI_VERSION = 8                  # include/shotvae_hip.h: SV_ABI_VERSION
 MAX_TAPS, MAX_PHASES = 16, 4
 DIST_KL, DIST_W2, DIST_EUCLID, DIST_COSINE = 0, 1, 2, 3      # include/shotvae_hip.h: SV_DIST_*
+CAL_LOGIT, CAL_PROB = 0, 1                                    # include/shotvae_hip.h: SV_CAL_*
 
 
 class SvPhase(C.Structure):
@@ -176,6 +177,12 @@ _PROTOS = {
     "sv_kmeans_accum": [P, P, P, I, I, I, P, P, P, I, I, P],
     "sv_kmeans_finish": [P, P, P, I, I, I, P, P, P, P, P],
     "sv_contingency": [P, P, I, I, I, P, P, P],
+    "sv_calib_rows": [I, P, I, I, I, P, P, P, P, P, P, P, P],
+    "sv_calib_accum": [P, P, P, P, P, P, I, I, P, I, P, P, P, P, I, I, P],
+    "sv_calib_finish": [P, P, P, P, I, I, P, P, P],
+    "sv_temp_accum": [I, P, I, I, I, P, P, P, P, I, I, P],
+    "sv_temp_update": [P, P, I, P, P, P, P],
+    "sv_rank_scan": [P, I, P, P, I, I, P, P, P],
     "sv_elbo_fwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P],
     "sv_elbo_bwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P, P, P, P, P],
     "sv_cls_fwd": [P, P, P, I, I, P, P],
