@@ -688,6 +688,67 @@ int sv_temp_accum(int kind, const float* x, int ldx, int N, int K, const int64_t
 int sv_temp_update(const double* sums, const int64_t* count, int P, double* beta, float* temp, float* stats, void* stream);
 int sv_rank_scan(const float* q, int Q, const float* g, const int64_t* g_w, int N, int P, int64_t* greater, int64_t* equal, void* stream);
 
+/* ---- t-SNE of the latent space: input affinities and one exact gradient-descent iteration (tsne.hip) --------------
+ * Added under ABI 8: new symbols only.  van der Maaten & Hinton 2008 with the sparse input affinities of van der Maaten 2014; the
+ * defaults of the Python layer are scikit-learn 1.7's.  d_ij is the value the index's metric gives the pair, used as is (the squared
+ * Euclid distance, KL, W2).  The embedding y is fp32 [N][d], d in {2, 3}.
+ *
+ * sv_tsne_affinity: dist fp32 [N][k], idx int64 [N][k]: a row's k-list, closest first.  A slot with idx < 0 or a dist that is not
+ *   finite is INVALID: p = 0.  Over the valid slots, with x_j = (double)d_ij - (double)d_i,min,
+ *       p_j|i = e_j / S,   e_j = exp(-beta_i x_j)  (1 where x_j == 0, whatever beta_i),   S = sum_j e_j
+ *       H_i   = log S + beta_i (sum_j x_j e_j) / S        (the Shannon entropy of p_.|i in nats; 0 for the second term when its sum is 0)
+ *   beta_i by scikit-learn's bisection, everything in double: beta = 1, bracket (-inf, +inf); at most max_steps evaluations of H; stop
+ *   when |H - log(perplexity)| <= tol; H too large: lo = beta, beta = 2 beta while hi = +inf, else (beta + hi) / 2; H too small: hi =
+ *   beta, beta = beta / 2 while lo = -inf, else (beta + lo) / 2.  After the last evaluation beta is NOT moved again:
+ *       p      fp32   [N][k]   the double results at the returned beta, rounded once
+ *       beta   double [N]      the beta of the last evaluation
+ *       steps  int32  [N]      the number of evaluations when the stop rule was met; max_steps when it never was
+ *   A row with fewer than two valid slots: p = 1 on its valid slot (if any), beta = 1, steps = max_steps.  A sum over the row: slot j
+ *   belongs to lane j mod 64, a lane adds its slots in slot order, the 64 lane sums meet in a butterfly (xor 32, .., 1).  A row's result
+ *   depends on that row alone.  1 <= k <= 256, 1 < perplexity < k, tol >= 0, max_steps >= 1.
+ *
+ * Low-dimensional side: r2_ij = sum_c (y_ic - y_jc)^2 over the differences themselves, explicit fmaf from 0 in dimension order;
+ *   w_ij = 1 / (1 + r2_ij) by the HARDWARE RECIPROCAL AND ONE NEWTON STEP, w = fma(w0, fma(-a, w0, 1), w0) with a = 1 + r2: exact where
+ *   1 / a is a power of two.  Z = sum over i != j of w_ij.  A pair is left out because i == j AS INDICES, never because r2 == 0:
+ *   duplicated points repel with force 0 and count 1 each into Z.  The joint P = (P_cond + P_cond^T) / (2N) comes as CSR (rowptr int64
+ *   [N + 1], non-decreasing from 0; col int64; val fp32): shot_vae_amd.embed.symmetrize.
+ *
+ * sv_tsne_attract: per row i over ITS segment q = rowptr[i] .. rowptr[i + 1] - 1, j = col[q], P = val[q] (an entry with j outside [0, N)
+ *   is skipped):
+ *       attr[i][c] = (float) sum_q (double)((P w_ij) (y_ic - y_jc))                                               (fp32 [N][d])
+ *       rowkl[i]   = (float) sum_q (double)(P logf(P (1 + r2_ij)))      over the entries with P > 0                (fp32 [N])
+ *   each term in fp32, the sums in double: lane s of the row's eight lanes adds the entries s, s + 8, .. in order, the eight lane sums meet
+ *   in a butterfly (xor 4, 2, 1).  Degrees are unbounded.  No scatter, no atomic; a row's result is a function of its segment and y.
+ *
+ * sv_tsne_repulse: the all-pairs scan.  Column tile t (64 points) goes to partial state t mod P (sv_kmeans_accum's rule):
+ *       rep[p][i][c] = sum_j w_ij^2 (y_ic - y_jc)     z[p][i] = sum_j w_ij       over the columns j != i of state p's tiles
+ *   in fp32, IN COLUMN ORDER (rep by fmaf(w^2, y_ic - y_jc, .), z by one add per column) from 0.       (fp32 [P][N][d], fp32 [P][N])
+ *   Columns >= N are masked out (w = 0), not placed far away.  The [N][N] matrix never exists.  1 <= P <= 64.
+ *
+ * sv_tsne_update: hyper is a DEVICE fp32 [3] = (exaggeration e, momentum, learning rate), read on the device: a captured call follows
+ *   a rewritten hyper.  With R_ic = sum_p rep[p][i][c] and Z_i = sum_p z[p][i] in double in index order, nb = ceil(N / 256) and
+ *   SUM(v) = the blocks' binary trees over 256 rows each, the nb block values added by thread t = b mod 256 in index order and one more
+ *   tree (a fixed order that depends on N alone), all in double:
+ *       Z        = SUM(Z_i)               g_ic = 4 (e attr[i][c] - R_ic / Z)    (the second term 0 when Z is not > 0: N = 1)
+ *       inc      = (double)vel * g < 0    gain = max(inc ? gain + 0.2f : gain * 0.8f, 0.01f)                        (fp32)
+ *       vel      = (float)(momentum vel - lr gain g)     in double, rounded once;      y += vel      (fp32; no recentring)
+ *       stats[0] = (float)(SUM(rowkl[i]) + log Z)   the KL of the UNEXAGGERATED P at the y the call STARTED from
+ *       stats[1] = (float)Z        stats[2] = (float)SUM(sum_c g_ic^2)                                             (fp32 [3])
+ *   y, vel and gain are updated in place.  scratch: caller-provided double [3 nb] (shot_vae_amd.embed.update_scratch(N)), overwritten.
+ *   Three launches.  y must be finite, and so must every r2 (|y| < 1e19): a NaN or an overflow propagates into y and stats as NaN;
+ *   nothing loops on data, nothing hangs or faults on it.
+ *
+ * Validated before any HIP call (nothing launched): a NULL pointer (col and val are read only through rowptr), N < 1, k outside
+ * [1, 256], perplexity outside (1, k), tol < 0, max_steps < 1, P outside [1, 64]: SV_E_ARG; d outside {2, 3}: SV_E_SHAPE.  No atomics
+ * anywhere; each takes a stream and allocates nothing: capturable; a repeated call sequence gives the same bits.                    */
+int sv_tsne_affinity(const float* dist, const int64_t* idx, int N, int k, double perplexity, double tol, int max_steps, float* p,
+                     double* beta, int* steps, void* stream);
+int sv_tsne_attract(const float* y, int N, int d, const int64_t* rowptr, const int64_t* col, const float* val, float* attr, float* rowkl,
+                    void* stream);
+int sv_tsne_repulse(const float* y, int N, int d, int P, float* rep, float* z, void* stream);
+int sv_tsne_update(float* y, float* vel, float* gain, const float* attr, const float* rowkl, const float* rep, const float* z, int P, int N,
+                   int d, const float* hyper, double* scratch, float* stats, void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

@@ -183,6 +183,10 @@ _PROTOS = {
     "sv_temp_accum": [I, P, I, I, I, P, P, P, P, I, I, P],
     "sv_temp_update": [P, P, I, P, P, P, P],
     "sv_rank_scan": [P, I, P, P, I, I, P, P, P],
+    "sv_tsne_affinity": [P, P, I, I, C.c_double, C.c_double, I, P, P, P, P],
+    "sv_tsne_attract": [P, I, I, P, P, P, P, P, P],
+    "sv_tsne_repulse": [P, I, I, I, P, P, P],
+    "sv_tsne_update": [P, P, P, P, P, P, P, I, I, I, P, P, P, P],
     "sv_elbo_fwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P],
     "sv_elbo_bwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P, P, P, P, P],
     "sv_cls_fwd": [P, P, P, I, I, P, P],
