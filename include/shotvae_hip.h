@@ -749,6 +749,72 @@ int sv_tsne_repulse(const float* y, int N, int d, int P, float* rep, float* z, v
 int sv_tsne_update(float* y, float* vel, float* gain, const float* attr, const float* rowkl, const float* rep, const float* z, int P, int N,
                    int d, const float* hyper, double* scratch, float* stats, void* stream);
 
+/* ---- diagonal Gaussian mixtures on the latent space, fitted by fused EM (mixture.hip) ---------------------------
+ * Added under ABI 8: new symbols only.  Rows x are fp32 [N][D] with row stride D; every matrix has row stride = its width.
+ *   the model            logw fp32 [K] (log mixing weights; -inf: a component that takes part in nothing), mean [K][D], var [K][D]
+ *   the derived table    ivar [K][D], cst [K], cdf [K] -- what the scans and the sampler read
+ *
+ * THE VALUE OF A PAIR, the same bits wherever it is formed (one device function serves both scans):
+ *       v(i, k) = cst_k - 1/2 sum_d (x_id - mean_kd)^2 ivar_kd
+ *   under sv_pairdist's summation rule: direct differences, 16 dimensions in fp32 as fmaf(dm * dm, ivar_kd, .) in index order, the
+ *   16-blocks in double in index order, then (float) fma(-0.5, sum, (double) cst_k): rounded once.  cst_k = -inf gives v = -inf.  A
+ *   sum that is NaN or infinite -- a row with a NaN or infinite entry -- gives v = NaN for every k.
+ *
+ * sv_gmm_prepare:  ivar = 1 / var in fp32;
+ *       cst_k = (float)(logw_k - 1/2 (D log 2 pi + sum_d log var_kd))      in double, d in index order, rounded once
+ *       cdf_k = (float)(sum_{j <= k} exp(logw_j) / sum_j exp(logw_j))      in double, index order, rounded once; the LAST component of
+ *               positive weight gets exactly 1
+ *   Between its two launches (cst[k], cdf[k]) carry the two halves of the double sum_d log var_kd.
+ *
+ * sv_gmm_estep:  lse[i] = log sum_k exp v(i, k) as an online log-sum-exp over tiles of 64 components in index order: the maximum in fp32,
+ *   the sum in double, expf on fp32 differences; lse = (float)((double) max + log(sum)), rounded once.       (fp32 [N])
+ *       assign[i] = the smallest k that attains the maximum over the FINITE v(i, .)                         (int64 [N], may be NULL)
+ *       resp[i][k] = expf(v(i, k) - lse[i])                                                                 (fp32 [N][K], may be NULL)
+ *   A row with a NaN or infinite entry gives lse = NaN, assign = -1 and a NaN resp row; a row for which every component has weight 0
+ *   gives lse = -inf, assign = -1.  K is tiled: any K >= 1; the [N][K] matrix exists only when resp is passed.  A row's result does not
+ *   depend on the rows around it: rows cut into calls give the same bits.
+ *
+ * sv_gmm_accum:  recomputes v and r_ik = expf(v(i, k) - lse[i]) -- bit-equal to sv_gmm_estep's resp -- and adds into P partial states
+ *   under sv_kmeans_accum's rule: tile t of 64 rows goes to state t mod P; inside a state the rows are added in index order.  State p is
+ *   sums + p (K (2 D + 1) + 1), doubles:
+ *       [k (2 D + 1)]                  += (double) r
+ *       [k (2 D + 1) + 1 + d]          += (double) r * (double) x_d                       (the product is exact)
+ *       [k (2 D + 1) + 1 + D + d]      += ((double) r * (double) x_d) * (double) x_d      (the second product rounded, then added)
+ *       [K (2 D + 1)]  -- THE LAST DOUBLE OF THE STATE --  += (double) lse[i]   over the finite rows, in row order
+ *   one double add per (row, accumulator), never fused with the products; and counts int64 [P][2]: [p][0] += the rows added, [p][1] += the
+ *   rows skipped because lse[i] is not finite.  init != 0 zeroes the states first; with init == 0 they continue.  Hence a repeated call
+ *   gives the same bits; with P = 1 the rows may be cut at any multiple of 64, with P > 1 at any multiple of 64 P, and the states hold the
+ *   bits of the one call.  No atomic of any kind.  1 <= P <= 64; D <= 2^20 (a block owns 32 dimensions: the grid's second dimension) and
+ *   K (2 D + 1) < 2^31 (SV_E_SHAPE beyond).
+ *
+ * sv_gmm_finish:  scikit-learn's M-step for covariance_type="diag", in double, the P states merged in index order, IN PLACE on the model:
+ *       n_k    = sum_p r-sums + 10 DBL_EPSILON         mean_kd = (float)(S1_kd / n_k)
+ *       var_kd = (float)((S2_kd / n_k - (S1_kd / n_k)^2) + reg_covar)                     logw_k = (float) log(n_k / sum_k n_k)
+ *   and then ivar, cst, cdf from those fp32 values as sv_gmm_prepare writes them.  A component whose r-sums add up to exactly 0 keeps its
+ *   mean and var, gets logw = -inf and has no share in sum_k n_k.  stats fp32 [4]:
+ *       [0] the mean of lse over the finite rows (scikit-learn's lower_bound_ at the parameters the E-step used; NaN without a finite row)
+ *       [1] the number of finite rows      [2] the number of skipped rows      [3] the smallest var written (+inf if none was)
+ *
+ * sv_gmm_sample:  z[b][d] = fmaf(sqrtf(var[c][d]), n(row0 + b, d), mean[c][d]), n = sv_latent_draw's counter and Box-Muller mapping under
+ *   SV_GMM_PHILOX_TAG (disjoint from the draw, score and dropout streams).  c = the first k with cdf_k > u (K - 1 if there is none),
+ *       u = (r[0] >> 8) * 2^-24,   r = Philox-4x32-10(counter = (low32(row), high32(row), 0xFFFFFFFF, SV_GMM_PHILOX_TAG), key = *key)
+ *   D <= 2^30 keeps d >> 2 away from 0xFFFFFFFF (SV_E_SHAPE beyond).  key is an int64 read FROM DEVICE MEMORY (required).  A row depends
+ *   only on (key, row0 + b).  comp (int64 [B], may be NULL) returns c.  A component of weight 0 is never drawn.
+ *
+ * Validated before any HIP call (SV_E_ARG / SV_E_SHAPE, nothing launched): a null pointer other than assign, resp, comp; a size < 1; P
+ * outside [1, 64]; a negative row0; reg_covar negative or not finite; the limits above.  Each takes a stream and allocates nothing:
+ * capturable; a repeated call sequence gives the same bits.                                                                          */
+#define SV_GMM_PHILOX_TAG 0x474D4D58u
+int sv_gmm_prepare(const float* logw, const float* mean, const float* var, int K, int D, float* ivar, float* cst, float* cdf, void* stream);
+int sv_gmm_estep(const float* x, int N, const float* ivar, const float* mean, const float* cst, int K, int D, float* lse, int64_t* assign,
+                 float* resp, void* stream);
+int sv_gmm_accum(const float* x, const float* lse, int N, const float* ivar, const float* mean, const float* cst, int K, int D, double* sums,
+                 int64_t* counts, int P, int init, void* stream);
+int sv_gmm_finish(const double* sums, const int64_t* counts, int P, int K, int D, double reg_covar, float* logw, float* mean, float* var,
+                  float* ivar, float* cst, float* cdf, float* stats, void* stream);
+int sv_gmm_sample(const float* mean, const float* var, const float* cdf, int K, int D, const int64_t* key, int64_t row0, int B, float* z,
+                  int64_t* comp, void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

@@ -23,4 +23,5 @@ from .cluster import (KMeans, kmeans_plus_plus, contingency, linear_assignment, 
 from .calibration import (row_stats, Reliability, TemperatureScaler, rank_counts, detection_metrics,      # noqa: F401
                           selective_metrics, evaluate_calibration, evaluate_detection)
 from .embed import TSNE, conditional_affinities, symmetrize, pca_project, evaluate_embedding      # noqa: F401
+from .mixture import GaussianMixture, evaluate_mixture, generate_from_mixture      # noqa: F401
 from .trace import StepLogger, step_range, enable_ranges     # noqa: F401

@@ -187,6 +187,11 @@ _PROTOS = {
     "sv_tsne_attract": [P, I, I, P, P, P, P, P, P],
     "sv_tsne_repulse": [P, I, I, I, P, P, P],
     "sv_tsne_update": [P, P, P, P, P, P, P, I, I, I, P, P, P, P],
+    "sv_gmm_prepare": [P, P, P, I, I, P, P, P, P],
+    "sv_gmm_estep": [P, I, P, P, P, I, I, P, P, P, P],
+    "sv_gmm_accum": [P, P, I, P, P, P, I, I, P, P, I, I, P],
+    "sv_gmm_finish": [P, P, I, I, I, C.c_double, P, P, P, P, P, P, P, P],
+    "sv_gmm_sample": [P, P, P, I, I, P, I64, I, P, P, P],
     "sv_elbo_fwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P],
     "sv_elbo_bwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P, P, P, P, P],
     "sv_cls_fwd": [P, P, P, I, I, P, P],

@@ -407,15 +407,17 @@ def evaluate_calibration(model, batches, bins=15, adaptive=False, temperature=No
     return rel.result(adaptive=adaptive)
 
 
-SCORES = ("msp", "entropy", "elbo", "log_px")
+SCORES = ("msp", "entropy", "elbo", "log_px", "mixture")
 
 
-def evaluate_detection(model, in_batches, out_batches, score="msp", criterion=None, tpr=0.95, **score_args):
+def evaluate_detection(model, in_batches, out_batches, score="msp", criterion=None, tpr=0.95, mixture=None, **score_args):
     """Out-of-distribution detection: does a per-image score of `model` separate the images of in_batches (the POSITIVE class) from
     those of out_batches (batches of images, or (image, ...) tuples, on the device)?
 
         "msp"      the maximum class probability (Hendrycks & Gimpel 2017)          "entropy"   minus the posterior's entropy
         "elbo"     SHOT-VAE's per-image ELBO                                        "log_px"    its importance-weighted log-likelihood
+        "mixture"  the log-density of the image's posterior mean under `mixture`, a mixture.GaussianMixture fitted to the codes of
+                   in-distribution data: one encoder pass, no decoder (a VariationalAutoEncoder or a SmoothVAE)
 
     The last two exist for a VariationalAutoEncoder only (score_terms with `criterion` and **score_args: samples, key, ...); for the
     other families they are refused with a ValueError before anything runs.  -> detection_metrics of all rows.  Eval mode only; no host
@@ -423,6 +425,10 @@ def evaluate_detection(model, in_batches, out_batches, score="msp", criterion=No
     if score not in SCORES:
         raise ValueError("evaluate_detection: score must be one of %s" % ", ".join(SCORES))
     family, posterior = _family("evaluate_detection", model)
+    if (score == "mixture") != (mixture is not None):
+        raise ValueError("evaluate_detection: score 'mixture' needs a fitted mixture, and only that score takes one")
+    if score == "mixture" and family == "classifier":
+        raise ValueError("evaluate_detection: score 'mixture' needs a latent code: a VariationalAutoEncoder or a SmoothVAE")
     if score in ("elbo", "log_px"):
         if family != "shot":
             raise ValueError("evaluate_detection: score %r needs a decoder with a per-image likelihood: a VariationalAutoEncoder, not %s"
@@ -444,6 +450,9 @@ def evaluate_detection(model, in_batches, out_batches, score="msp", criterion=No
                 if "row0" not in args and args.get("key") is not None:
                     args["row0"] = seen                     # every image its own draws, whatever the batching
                 v = model.score_terms(image, criterion, (score,), what="evaluate_detection", **args)[score]
+            elif score == "mixture":
+                from .neighbors import encode_posterior
+                v = mixture.score_samples(encode_posterior(model, image)[0])
             else:
                 x, kind = posterior(image)
                 stats = row_stats(x, kind=kind)

@@ -220,7 +220,7 @@ def frechet_distance(a, b):
     return frechet_from_moments(m1, s1, m2, s2)
 
 
-def evaluate_generation(model, batches, source="generate", space="mu", k=5, metric="euclid", key=0, tau=1.0):
+def evaluate_generation(model, batches, source="generate", space="mu", k=5, metric="euclid", key=0, tau=1.0, mixture=None):
     """The quality of what `model` (a VariationalAutoEncoder or a SmoothVAE, in eval mode: NotImplementedError otherwise, as for score)
     generates, against the images of `batches` ((image, label) or (image,) tuples, or image tensors, on the device).
 
@@ -228,6 +228,8 @@ def evaluate_generation(model, batches, source="generate", space="mu", k=5, metr
                                where a batch carries none), drawn with `key` and `tau` at row0 = the running index: the samples do not
                                depend on the batching
                 "reconstruct"  the reconstructions of the same images (the reconstruction Frechet distance)
+                "mixture"      as "generate", with the codes drawn from `mixture` (a fitted mixture.GaussianMixture) where "generate"
+                               draws them from the prior: generate_from_mixture with `key` at row0 = the running index (`tau` is not read)
         space   "mu"           both sets are compared by their posterior means (encode_posterior; "w2" also reads log sigma)
                 "features"     by the pooled encoder features (VariationalAutoEncoder only; "euclid" only: features have no sigma)
 
@@ -238,8 +240,10 @@ def evaluate_generation(model, batches, source="generate", space="mu", k=5, metr
     from .vae import VariationalAutoEncoder
     if not isinstance(model, (VariationalAutoEncoder, SmoothVAE)):
         raise TypeError("evaluate_generation: a VariationalAutoEncoder or a SmoothVAE, not %s" % type(model).__name__)
-    if source not in ("generate", "reconstruct"):
-        raise ValueError("evaluate_generation: source must be 'generate' or 'reconstruct'")
+    if source not in ("generate", "reconstruct", "mixture"):
+        raise ValueError("evaluate_generation: source must be 'generate', 'reconstruct' or 'mixture'")
+    if (source == "mixture") != (mixture is not None):
+        raise ValueError("evaluate_generation: source='mixture' needs a fitted mixture, and only that source takes one")
     if space not in ("mu", "features"):
         raise ValueError("evaluate_generation: space must be 'mu' or 'features'")
     code = _ball_metric("evaluate_generation", metric)
@@ -269,11 +273,15 @@ def evaluate_generation(model, batches, source="generate", space="mu", k=5, metr
         for t in (image, label):
             if torch.is_tensor(t) and not t.is_cuda:
                 raise L.ShotVaeHipError("evaluate_generation: input is not on an MI355X (no CPU fallback)")
-        if source == "generate":
+        if source in ("generate", "mixture"):
             label = model.predict(image) if label is None else label.reshape(-1).long()
             if label.numel() != image.shape[0]:
                 raise ValueError("evaluate_generation: %d labels for %d images" % (label.numel(), image.shape[0]))
-            made = model.generate(label, key, tau=tau, row0=count)
+            if source == "mixture":
+                from .mixture import generate_from_mixture
+                made = generate_from_mixture(model, mixture, label, key, row0=count)
+            else:
+                made = model.generate(label, key, tau=tau, row0=count)
         else:
             made = model.reconstruct(image)
         r_mu, r_ls = rows_of(image)
