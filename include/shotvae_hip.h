@@ -815,6 +815,63 @@ int sv_gmm_finish(const double* sums, const int64_t* counts, int P, int K, int D
 int sv_gmm_sample(const float* mean, const float* var, const float* cdf, int K, int D, const int64_t* key, int64_t row0, int B, float* z,
                   int64_t* comp, void* stream);
 
+/* ---- linear probes on the latent space: fused softmax regression (probe.hip) -------------------------------------
+ * Added under ABI 8: new symbols only.  Rows x are fp32 [N][D] with row stride D; every matrix has row stride = its width.
+ *   the model the scans read     w fp32 [K][D], b fp32 [K]
+ *   the iterates                 theta, look double [K][D + 1]: element [k][0] is the intercept, [k][1 + d] the weight of dimension d
+ *   the objective                F = 1/n sum_i (lse_i - v(i, y_i)) + lambda / 2 sum_kd w_kd^2 over the n used rows; the intercept is not
+ *                                penalised.  lambda = 1 / (C n) makes it scikit-learn's LogisticRegression(C=C) objective over C n.
+ *
+ * THE SCORE OF A PAIR, the same bits wherever it is formed (one device function serves both scans):
+ *       v(i, k) = b_k + sum_d x_id w_kd
+ *   under sv_pairdist's summation rule: 16 dimensions in fp32 as fmaf(x_id, w_kd, .) in index order, the 16-blocks in double in index
+ *   order, then (float)(sum + (double) b_k): rounded once.  A sum that is NaN or infinite -- a row with a NaN or infinite entry -- gives
+ *   v = NaN for every k.
+ *
+ * sv_probe_rows:  lse[i] = log sum_k exp v(i, k) as an online log-sum-exp over tiles of 64 classes (16 for K <= 16) in index order: the
+ *   maximum in fp32, the sum in double, expf on fp32 differences; lse = (float)((double) max + log(sum)), rounded once.     (fp32 [N])
+ *       loss[i]  = lse[i] - v(i, label[i]) in fp32; NaN where label[i] is outside [0, K)               (fp32 [N], may be NULL; needs label)
+ *       pred[i]  = the smallest k that attains the maximum of v(i, .)                                  (int64 [N], may be NULL)
+ *       proba[i][k] = expf(v(i, k) - lse[i]), from a second pass over the tiles                        (fp32 [N][K], may be NULL)
+ *   label is int64 [N] and may be NULL when loss is.  A row with a NaN or infinite entry gives lse = NaN, loss = NaN, pred = -1 and a NaN
+ *   proba row.  K is tiled: any K >= 2; the [N][K] matrix exists only when proba is passed.  A row's result does not depend on the rows
+ *   around it: rows cut into calls give the same bits.
+ *
+ * sv_probe_accum:  recomputes v and r_ik = expf(v(i, k) - lse[i]) - [k == label[i]] in fp32, the subtraction rounded once -- expf(.) is
+ *   bit-equal to sv_probe_rows' proba -- and adds into P partial states under sv_kmeans_accum's rule: tile t of 64 rows goes to state
+ *   t mod P; inside a state the rows are added in index order.  A row is USED iff lse[i] is finite and label[i] is in [0, K); every other
+ *   row is skipped.  State p is sums + p (K (D + 1) + 1), doubles:
+ *       [k (D + 1)]              += (double) r                                   (the intercept's gradient)
+ *       [k (D + 1) + 1 + d]      += (double) r * (double) x_d                    (the product is exact)
+ *       [K (D + 1)]  -- THE LAST DOUBLE OF THE STATE --  += (double) loss[i]     over the used rows, in row order
+ *   one double add per (row, accumulator), never fused with the product; and counts int64 [P][2]: [p][0] += the rows used, [p][1] += the
+ *   rows skipped.  init != 0 zeroes the states first; with init == 0 they continue.  Hence a repeated call gives the same bits; with
+ *   P = 1 the rows may be cut at any multiple of 64, with P > 1 at any multiple of 64 P, and the states hold the bits of the one call.
+ *   resid (fp32 [N][K], may be NULL) receives r (0 for a skipped row).  No atomic of any kind.  1 <= P <= 64; D <= 2^20 (a block owns
+ *   32 dimensions: the grid's second dimension) and K (D + 1) < 2^31 (SV_E_SHAPE beyond).
+ *
+ * sv_probe_update:  one step of Nesterov's method with constant momentum, in double, every operation rounded once, in two launches.
+ *   With n = sum_p counts[p][0] and G = the P states added in index order (from 0):
+ *       g_k0 = G_k0 / n                         g_k,1+d = G_k,1+d / n + lambda look_k,1+d            (the gradient of F at look)
+ *   g is written INTO STATE 0 of sums (the states are consumed: the next sv_probe_accum starts with init != 0), and the class's partials
+ *   max_e |g_ke| and sum_d look_k,1+d^2 go to stats[4 + 2 k], stats[5 + 2 k]; thread t of 256 adds its elements e = t, t + 256, ... in
+ *   index order and thread 0 adds the 256 shares in index order.  Then, element by element,
+ *       theta_new = look - inv_L g              look_new = theta_new + beta (theta_new - theta)
+ *   are written in place, with b_k = (float) look_new_k0 and w_kd = (float) look_new_k,1+d.  stats is double [4 + 2 K]:
+ *       [0] F at the OLD look: (sum_p loss sums) / n + 0.5 (lambda sum_k stats[5 + 2 k]), p and k in index order
+ *       [1] max_k stats[4 + 2 k]                [2] n, the rows used                [3] the rows skipped
+ *   With n = 0 neither theta, look, w nor b is written, and stats[0] = stats[1] = NaN.
+ *
+ * Validated before any HIP call (SV_E_ARG / SV_E_SHAPE, nothing launched): a null pointer other than label (without loss), loss, pred,
+ * proba, resid; N or D < 1; K < 2; P outside [1, 64]; lambda or inv_L not finite or <= 0; beta outside [0, 1); the limits above.  Each
+ * takes a stream and allocates nothing: capturable; a repeated call sequence gives the same bits.                                     */
+int sv_probe_rows(const float* x, int N, const float* w, const float* b, int K, int D, const int64_t* label, float* lse, float* loss,
+                  int64_t* pred, float* proba, void* stream);
+int sv_probe_accum(const float* x, const int64_t* label, const float* lse, const float* loss, int N, const float* w, const float* b, int K,
+                   int D, double* sums, int64_t* counts, int P, int init, float* resid, void* stream);
+int sv_probe_update(double* sums, const int64_t* counts, int P, int K, int D, double lambda, double inv_L, double beta, double* theta,
+                    double* look, float* w, float* b, double* stats, void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

@@ -192,6 +192,9 @@ _PROTOS = {
     "sv_gmm_accum": [P, P, I, P, P, P, I, I, P, P, I, I, P],
     "sv_gmm_finish": [P, P, I, I, I, C.c_double, P, P, P, P, P, P, P, P],
     "sv_gmm_sample": [P, P, P, I, I, P, I64, I, P, P, P],
+    "sv_probe_rows": [P, I, P, P, I, I, P, P, P, P, P, P],
+    "sv_probe_accum": [P, P, P, P, I, P, P, I, I, P, P, I, I, P, P],
+    "sv_probe_update": [P, P, I, I, I, C.c_double, C.c_double, C.c_double, P, P, P, P, P, P],
     "sv_elbo_fwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P],
     "sv_elbo_bwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P, P, P, P, P],
     "sv_cls_fwd": [P, P, P, I, I, P, P],
