@@ -1148,6 +1148,16 @@ int sv_debug_wgrad_tile_program(int halo_vectors, int* items, int* waits);
  * taps 1, 4, 7 (each = the younger LDS-DMA instructions only: zero).                                               */
 int sv_debug_conv_chunk_program(int* items, int* waits);
 
+/* The work table of the per-pixel GEMM kernel (pixgemm.hip) for geometry g -- ConvTranspose2d(4, 2, 1) forward on maps of up to
+ * 4 x 4 pixels, or its data gradient (a 4x4 stride-2 pad-1 convolution) on maps of up to 8 x 8; SV_E_SHAPE for anything else.
+ * *npix = output pixels; in the kernel's work order (falling tap count) pixels = int[64][4] {oy, ox, phase, valid taps} and
+ * taps = int[64][16][4] {tap index inside the phase, iy, ix, element offset of the tap's [Cin] slice in row 0 of the packed
+ * weights (phase[].w_off + tap * Cin; row n adds n * phase[].ntap * Cin)}, -1 beyond the pixel's valid taps.               */
+int sv_debug_pixgemm_table(const sv_geom* g, int* npix, int* pixels, int* taps);
+/* The label of the calling thread's last launch of the sv_igemm family ("sv_igemm", "sv_igemm(dma)", "sv_igemm(pixel)", ...; ""
+ * before the first) as a C string in buf[len]: tests assert which kernel a dispatch took.  A grid query launches nothing. */
+int sv_debug_last_kernel(char* buf, int len);
+
 /* ---- dispatcher options (process-wide; set them between launches, not concurrently with them) --------------------
  * SV_OPT_DISABLE_MASK: OR of SV_K_* bits; a set bit routes the layers a specialised kernel would take to the next more
  * general one (sv_igemm: conv3x3x -> conv3x3w -> conv3x3 / conv3x3p / conv3x3m -> halo -> the generic gather-GEMM; sv_wgrad:
@@ -1181,8 +1191,9 @@ enum { SV_OPT_DISABLE_MASK = 0, SV_OPT_WIDE_MIN_BLOCKS = 1, SV_OPT_HALO_ALL = 2,
 enum { SV_K_CONV3X3 = 1, SV_K_CONV3X3P = 2, SV_K_CONV3X3M = 4, SV_K_CONV3X3W = 8, SV_K_CONV3X3X = 16,
        SV_K_WGRAD3X3 = 32, SV_K_WGRAD3X3W = 64, SV_K_IGEMM_KV2 = 128, SV_K_HALO = 256, SV_K_HALOP = 512, SV_K_HWGRAD = 1024, SV_K_IGEMM_BIG = 2048, SV_K_WGRAD_WIDE = 4096, SV_K_IGEMM_ALIGNED = 8192, SV_K_IGEMM_DMA = 16384, SV_K_WGRAD_INCR = 32768, SV_K_WGRAD3X3M = 65536, SV_K_TCONVR = 131072, SV_K_TCONVR_EX = 262144, SV_K_SCONV = 524288, SV_K_PCONV = 8388608, SV_K_THCONV = 16777216, SV_K_THWGRAD = 67108864, SV_K_S2WGRAD = 134217728,
        SV_K_MAP4 = 268435456,      /* wgrad3x3 on 4 x 4 maps (ON by default: 236 against 405 us at 512 -> 512, 4 x 512 images) */
-       SV_K_MAP4_CONV = 536870912  /* conv3x3 (forward / data gradient) on 4 x 4 maps: OFF by default (SV_OPT_ENABLE_MASK) -- measured
-                                      224 against 235 us forward (inside the run-to-run spread), 191 against 161 us data gradient */ };
+       SV_K_MAP4_CONV = 536870912, /* conv3x3 (forward / data gradient) on 4 x 4 maps: OFF by default (SV_OPT_ENABLE_MASK) -- measured
+                                      224 against 235 us forward (inside the run-to-run spread), 191 against 161 us data gradient */
+       SV_K_PIXGEMM = 1073741824   /* per-pixel GEMMs for ConvTranspose2d(4, 2, 1) on maps <= 4 x 4 and its data gradient (pixgemm.hip) */ };
 int sv_set_option(int key, int value);
 int sv_get_option(int key);          /* -1 for an unknown key */
 

@@ -237,6 +237,8 @@ _PROTOS = {
     "sv_prof_collect": [I, C.POINTER(C.c_double), C.POINTER(C.c_int)],
     "sv_debug_wgrad_tile_program": [I, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "sv_debug_conv_chunk_program": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "sv_debug_pixgemm_table": [C.POINTER(SvGeom), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "sv_debug_last_kernel": [C.c_char_p, I],
     "sv_set_option": [I, I],
     "sv_get_option": [I],
     "sv_bn_bwd_affine": [P, I, I, F, P, P, P, P, P, P, P, P, I, P],
@@ -258,6 +260,7 @@ OPT_DISABLE_MASK, OPT_WIDE_MIN_BLOCKS, OPT_HALO_ALL, OPT_PERSISTENT_BLOCKS, OPT_
 K_PCONV, K_THCONV, K_THWGRAD, K_S2WGRAD = 1 << 23, 1 << 24, 1 << 26, 1 << 27
 K_MAP4 = 1 << 28           # wgrad3x3 on 4 x 4 maps (the last stage of the PreActResNets); on by default (disable mask)
 K_MAP4_CONV = 1 << 29      # conv3x3 forward / data gradient on 4 x 4 maps; OFF by default (enable mask): it did not beat the gather-GEMM
+K_PIXGEMM = 1 << 30        # per-pixel GEMMs for ConvTranspose2d(4, 2, 1) on maps <= 4 x 4 and its data gradient (pixgemm.hip)
 EXPORTS = sorted(list(_PROTOS) + ["sv_last_error"])
 
 _lib = None
@@ -326,7 +329,7 @@ class options:
 # launch under a per-layer tag first (Engine._tag, for sv_igemm / sv_wgrad)
 prof_tags = None
 _LAYER_TAGGED = ("sv_igemm", "sv_igemm_query_blocks", "sv_wgrad", "sv_wgrad_ex", "sv_bwd3x3", "sv_dropout_fwd", "sv_prof_tag", "sv_prof_enable",
-                 "sv_set_option")
+                 "sv_set_option", "sv_debug_last_kernel")
 
 
 def deterministic():
@@ -366,6 +369,13 @@ def check_flag_timeouts(where=""):
             "momentum buffer cannot be trusted: restore the last checkpoint, do not save one.  Kernel dispatch is serialised or the "
             "main queue stalled > 3 s (profiler, debugger, shared GPU): set Engine.flag_fork = False (event forks) and re-run.  (The "
             "counter stays set until sv_flag_timeouts_reset(): every later step raises too.)" % (n, (" (" + where + ")") if where else ""))
+
+
+def last_kernel():
+    """label of this thread's last launch of the sv_igemm family (sv_debug_last_kernel)"""
+    buf = C.create_string_buffer(64)
+    call("sv_debug_last_kernel", buf, 64)
+    return buf.value.decode()
 
 
 def call(name, *args):

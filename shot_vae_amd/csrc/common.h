@@ -362,6 +362,8 @@ inline sv_igemm_args sv_fold_resolve(const sv_igemm_args& a, bool can) {
     if (!sv_fold_claim(can)) b.fold_stats = nullptr;
     return b;
 }
+// the label of the calling thread's last launch through sv_igemm_launch (sv_debug_last_kernel: tests name the kernel that ran)
+void sv_note_kernel(const char* label);
 // The one launch path of the sv_igemm family: the gate (sv_dry_run -- a grid query, the deterministic replica check and the
 // materialisation of an unclaimed fold; its rc is returned when nothing is to be launched), then `kernel` on grid_x x groups
 // blocks of `threads` threads with (*g, the per-group argument blocks, extra...).  `es`: the element size of x / out.
@@ -370,6 +372,7 @@ inline int sv_igemm_launch(K* kernel, int grid_x, int threads, size_t lds, const
                            hipStream_t s, const char* label, X... extra) {
     int rc = SV_OK;
     if (sv_dry_run(grid_x, a, &rc)) return rc;
+    sv_note_kernel(label);
     sv_prof_begin(s);
     hipLaunchKernelGGL(kernel, dim3(grid_x, sv_ngroups(a->groups)), dim3(threads), lds, s, *g, sv_expand_groups(*g, *a, es), extra...);
     sv_prof_end(s);
@@ -408,7 +411,7 @@ void sv_slab_reduce(const float* ws, int nslabs, int64_t n, float* dw, hipStream
 // The specialised candidates of sv_igemm (igemm.hip, whose generic kernels are its tail): each returns 1 and sets *rc when it
 // takes the launch.  (sv_conv3x3_try tries sv_conv3x3w_try first, which tries sv_conv3x3x_try.)
 typedef int sv_igemm_try_fn(const sv_geom* g, int dtype, const sv_igemm_args* a, hipStream_t s, int* rc);
-sv_igemm_try_fn sv_conv3x3_try, sv_halo_try, sv_tconvr_try, sv_sconv_try, sv_pconv_try, sv_dconv_try, sv_thconv_try, sv_conv3x3w_try;
+sv_igemm_try_fn sv_conv3x3_try, sv_halo_try, sv_tconvr_try, sv_sconv_try, sv_pconv_try, sv_dconv_try, sv_thconv_try, sv_conv3x3w_try, sv_pixgemm_try;
 int sv_conv3x3x_try(const sv_geom* g, const sv_igemm_args* a, bool fwd, hipStream_t s, int* rc);
 // The specialised candidates of the weight-gradient dispatch (wgrad.hip, whose generic kernels are its tail with the same
 // signature), in its order: each returns 1 and sets *rc when it takes the launch.  `a` is the checked operand block with

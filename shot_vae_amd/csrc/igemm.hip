@@ -609,6 +609,9 @@ extern "C" int sv_igemm(const sv_geom* g, int dtype, const sv_igemm_args* a_in, 
         if (sv_sconv_try(g, dtype, a, s, &rc)) return rc;
         // the other conv-like layers with a spatial extent: LDS-halo gather-GEMM over all phases / taps (halo.hip)
         if (sv_halo_try(g, dtype, a, s, &rc)) return rc;
+        // ConvTranspose2d(4, 2, 1) on maps of up to 4 x 4 pixels and its data gradient, without a load prologue: one exact GEMM
+        // per output pixel over its valid taps (pixgemm.hip)
+        if (sv_pixgemm_try(g, dtype, a, s, &rc)) return rc;
     }
     const int64_t M = (int64_t)g->B * g->Hq * g->Wq;
     // wide layers (N a multiple of 160 / 128) with enough rows: 256-row tiles at two blocks per CU -- the input is gathered
@@ -619,11 +622,13 @@ extern "C" int sv_igemm(const sv_geom* g, int dtype, const sv_igemm_args* a_in, 
         // no load prologue (data gradients): both operands by LDS-DMA
         const bool dma = !a->pro_scale && g->Cin % 32 == 0 && g->ldx % 8 == 0 && !sv_disabled(SV_K_IGEMM_DMA);
         if (dma && g->N % 160 == 0 && mt256 * (g->N / 160) >= sv_wide_min_blocks()) return launch_dma<10, 4>(g, a, s);
-        // Small products (the decoder's ConvTranspose layers and their data gradients): while the 256-row tiles give fewer
-        // than two blocks per CU, 128-row tiles of the WIDEST channel extent (128 / 64 / 32) that still yields two blocks per
-        // CU -- the kernel needs its second resident block to cover the k loop's latency -- else the narrowest one
-        // (measured at 4 x 512 / 2 x 512 images: ConvT 1024->512 forward 43 -> 36 us, 512->256 forward 74 -> 60,
-        //  512->256 data gradient 88 -> 69, 256->128 data gradient 68 -> 55, 128->64 data gradient 60 -> 44 us)
+        // Small products: while the 256-row tiles give fewer than two blocks per CU, 128-row tiles of the WIDEST channel extent
+        // (128 / 64 / 32) that still yields two blocks per CU -- the kernel needs its second resident block to cover the k loop's
+        // latency -- else the narrowest one.  The first three ConvTranspose layers of the decoder and their data gradients, for
+        // which this trade was made, now take the per-pixel GEMMs (pixgemm.hip); what still comes here: the same layers with
+        // SV_K_PIXGEMM disabled, with a load prologue or a bias (then 60-69 us at 4 x 512 / 2 x 512 images, against 10-20), the
+        // 128 -> 64 ConvTranspose's data gradient (8x8 <- 16x16: 60 -> 44 us on the narrow tiles), Linear-shaped 1x1 products and
+        // the small-batch launches of decode() / score().
         if (dma && g->N % 32 == 0 && mt256 * ((g->N + 127) / 128) < 2 * sv_wide_min_blocks()) {
             const int64_t mt128 = (M + 127) / 128 * g->nphase * sv_ngroups(a->groups);
             const int64_t two = 2 * sv_wide_min_blocks();

@@ -125,6 +125,13 @@ bool sv_dry_run(int grid_x, const sv_igemm_args* a, int* rc) {
     }
     return false;
 }
+static thread_local const char* tl_last_kernel = "";
+void sv_note_kernel(const char* label) { tl_last_kernel = label; }
+extern "C" int sv_debug_last_kernel(char* buf, int len) {
+    SV_REQUIRE(buf && len > 0, SV_E_ARG, "sv_debug_last_kernel: no buffer");
+    snprintf(buf, (size_t)len, "%s", tl_last_kernel);
+    return SV_OK;
+}
 struct SvQueryScope {
     explicit SvQueryScope(int* out) { tl_query_blocks = out; }
     ~SvQueryScope() { tl_query_blocks = nullptr; }
