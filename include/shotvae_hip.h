@@ -872,6 +872,63 @@ int sv_probe_accum(const float* x, const int64_t* label, const float* lse, const
 int sv_probe_update(double* sums, const int64_t* counts, int P, int K, int D, double lambda, double inv_L, double beta, double* theta,
                     double* look, float* w, float* b, double* stats, void* stream);
 
+/* ---- label spreading and propagation on a CSR graph (labelprop.hip) -----------------------------------------------
+ * Added under ABI 8: new symbols only.  The graph is the CSR form embed.symmetrize returns and sv_tsne_attract reads: rowptr int64
+ * [N + 1], col int64 [nnz], val fp32 [nnz].  A row's segment is [rowptr[i], rowptr[i + 1]) clamped to [0, nnz]; an entry whose column is
+ * outside the matrix is NO EDGE and is skipped: nothing is read outside the arrays whatever rowptr and col hold.  Weights are expected
+ * finite and >= 0; a NaN weight reaches the rows that read it and the statistics, nothing else.  col, val / sval may be NULL when
+ * nnz == 0.  Every matrix has row stride = its width.
+ *
+ * sv_lp_normalize (square graphs: columns in [0, N)), two launches:
+ *       deg[i]  = the sum of row i's valid weights in double: lane s of eight adds the valid entries s, s + 8, .. of the segment in
+ *                 order (from 0.0), the eight lane sums meet as ((l0 + l4) + (l2 + l6)) + ((l1 + l5) + (l3 + l7))       (double [N])
+ *       sval[q] = mode SV_LP_SYM:  w_q / sqrt(deg[i] deg[j])    (Zhou et al.'s D^-1/2 W D^-1/2; 0 where deg[i] deg[j] == 0)
+ *                 mode SV_LP_ROW:  w_q / deg[i]                 (D^-1 W; 0 where deg[i] == 0)
+ *                 product, root and quotient each rounded once in double, the result once to fp32; 0 for an entry that is no edge
+ *                 (fp32 [nnz]; entries outside every segment are not written)
+ *
+ * sv_lp_step: one iteration f_in fp32 [M][K] -> f_out fp32 [N][K] over a graph of N rows and M columns (M == N during a fit).
+ *       acc(i, c) = sum_q (double) sval[q] * (double) f_in[col[q]][c]  over row i's valid entries IN SEGMENT ORDER, from 0.0: every
+ *                   product is exact in double, every addition rounded once.
+ *   label is int64 [N]; a value outside [0, K) (-1 by convention) marks an unlabelled row.  With every operation rounded once in
+ *   double (no contraction) and the result once to fp32:
+ *       SV_LP_SPREADING     f_out = alpha * acc + (c == label[i] ? one_minus_alpha : 0.0)
+ *       SV_LP_PROPAGATION   a labelled row: the one-hot of its label; an unlabelled row: acc / s with s = the sum of acc(i, .) in CLASS
+ *                           ORDER from 0.0, s == 0 replaced by 1 (scikit-learn's per-iteration normalisation and hard clamp)
+ *       SV_LP_PRODUCT       f_out = acc; label may be NULL
+ *   Statistics (stats != NULL; needs scratch and M == N): every block of 256 threads -- 16 rows for K <= 16, else 4 -- leaves the sum and
+ *   the maximum of |(double) f_out - (double) f_in| over its elements in scratch[2 b], scratch[2 b + 1] (a thread's elements in class
+ *   order, then a binary tree over the threads); a one-block launch merges them -- thread t the blocks t, t + 256, .. in order, then the
+ *   same tree -- into stats[0] = delta_l1, stats[1] = delta_max (a NaN is kept by both).  scratch is double [2 ceil(N / rows per
+ *   block)].  A row's f_out is a function of its own segment and of the rows it names: rows cut into calls through offset pointers
+ *   (rowptr + r, label + r, f_out + r K; stats NULL) give the same bits.  f_out must not overlap f_in.  1 <= K <= 1024; the indices are
+ *   64-bit.
+ *
+ * sv_lp_finish: per row of f fp32 [N][K], s = the sum in class order in double, s' = (s == 0 ? 1 : s):
+ *       proba[i][c] = (float)((double) f[i][c] / s')                                                  (fp32 [N][K], may be NULL)
+ *       pred[i]     = the smallest c that attains the maximum of f[i][.]; -1 where s == 0 (no label reached the row) or the row holds
+ *                     a NaN                                                                           (int64 [N], may be NULL)
+ *       conf[i]     = proba at that c (the largest probability for s > 0)                             (fp32 [N], may be NULL)
+ *       counts      = {rows without a NaN and s != 0, rows without a NaN and s == 0}, from a one-block launch of its own
+ *                                                                                                     (int64 [2], may be NULL)
+ *   Every subset of the outputs gives the same bits in the others; at least one is required; proba must not be f.
+ *
+ * Validated before any HIP call (SV_E_ARG, nothing launched): a NULL required pointer, N or M < 1, nnz < 0, K outside [1, 1024], an
+ * unknown mode or variant, a NULL label outside the product variant, alpha or one_minus_alpha not finite under spreading, an f_out that
+ * overlaps f_in, stats without scratch or with M != N.  Each takes a stream and allocates nothing: capturable; no atomic of any kind; a
+ * repeated call sequence gives the same bits.                                                                                        */
+#define SV_LP_SYM 0
+#define SV_LP_ROW 1
+#define SV_LP_SPREADING 0
+#define SV_LP_PROPAGATION 1
+#define SV_LP_PRODUCT 2
+int sv_lp_normalize(const int64_t* rowptr, const int64_t* col, const float* val, int N, int64_t nnz, int mode, double* deg, float* sval,
+                    void* stream);
+int sv_lp_step(const float* f_in, int M, const int64_t* rowptr, const int64_t* col, const float* sval, int64_t nnz, int N, int K,
+               const int64_t* label, int variant, double alpha, double one_minus_alpha, float* f_out, double* scratch, double* stats,
+               void* stream);
+int sv_lp_finish(const float* f, int N, int K, float* proba, int64_t* pred, float* conf, int64_t* counts, void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

@@ -25,4 +25,5 @@ from .calibration import (row_stats, Reliability, TemperatureScaler, rank_counts
 from .embed import TSNE, conditional_affinities, symmetrize, pca_project, evaluate_embedding      # noqa: F401
 from .mixture import GaussianMixture, evaluate_mixture, generate_from_mixture      # noqa: F401
 from .probe import LinearProbe, evaluate_probe, select_labels      # noqa: F401
+from .propagate import LabelPropagator, knn_graph, normalize_graph, evaluate_propagation      # noqa: F401
 from .trace import StepLogger, step_range, enable_ranges     # noqa: F401
