@@ -18,7 +18,8 @@ import math
 import torch
 
 from . import _lib as L
-from .neighbors import LatentIndex, _p, _rows, _st
+from ._latent import _p, _st, eval_only, latent_family, on_device, split_batch
+from .neighbors import LatentIndex, posterior_rows
 
 MAX_PARTIALS = 64
 TARGET_BLOCKS = 1024          # four blocks per CU of an MI355X: the smallest P that reaches it
@@ -59,7 +60,7 @@ class AggregatePosterior:
         """-> (z [Q, dim], lqx [Q], lpz [Q]) fp32: z = mu + exp(ls) n(row0 + i, s, .) from the stream of score(samples=S, key=...) -- the
         draw that call uses for image row0 + i and sample s --, log q(z | x) and log p(z).  key: an int or a 1-element int64 device tensor;
         None: z = mu exactly."""
-        mu, ls = _rows("AggregatePosterior.sample", L.DIST_KL, mu, ls, dim=self.dim)
+        mu, ls = posterior_rows("AggregatePosterior.sample", L.DIST_KL, mu, ls, dim=self.dim)
         row0, s = int(row0), int(s)
         if row0 < 0 or not 0 <= s < 65536:
             raise ValueError("AggregatePosterior.sample: row0 must be >= 0 and s in [0, 65536)")
@@ -85,8 +86,7 @@ class AggregatePosterior:
         """-> lq [Q] = log q(z_i) = log 1/N sum_j N(z_i; mu_j, sigma_j^2), fp32; with per_dim also lq_d [Q, dim] = log q(z_id), the
         marginal of every dimension.  exclude_self_from = s: z_i was drawn from gallery row s + i, which is left out of its own sum
         (leave-one-out; the mean is then over N - 1 rows)."""
-        if torch.is_tensor(z) and not z.is_cuda:
-            raise L.ShotVaeHipError("AggregatePosterior.log_density: input is not on an MI355X (no CPU fallback)")
+        on_device("AggregatePosterior.log_density", z)
         if not torch.is_tensor(z) or z.dim() != 2 or z.shape[0] < 1 or z.shape[1] != self.dim:
             raise ValueError("AggregatePosterior.log_density: z must be a non-empty matrix [n, %d]" % self.dim)
         N = len(self.index)
@@ -139,28 +139,22 @@ def evaluate_aggregate(model, batches, samples=1, key=0, query_batches=None, per
 
     The sums over queries are float64 on the device; the one host read is at the end."""
     from .neighbors import encode_posterior
-    from .smooth import SmoothVAE
-    from .vae import VariationalAutoEncoder
-    if not isinstance(model, (VariationalAutoEncoder, SmoothVAE)):
-        raise TypeError("evaluate_aggregate: a VariationalAutoEncoder or a SmoothVAE, not %s" % type(model).__name__)
+    family = latent_family("evaluate_aggregate", model)
     samples = int(samples)
     if samples < 1 or samples > 65536:
         raise ValueError("evaluate_aggregate: samples must be in [1, 65536]")
     if key is None:
         raise ValueError("evaluate_aggregate: the samples need a key")
-    if model.training:
-        raise NotImplementedError("evaluate_aggregate is implemented for eval mode only (no noise, no gradients): call model.eval() first")
+    eval_only("evaluate_aggregate", model)
 
     def image_of(batch):
-        return batch[0] if isinstance(batch, (tuple, list)) else batch
+        return split_batch("evaluate_aggregate", batch, None)[0]
 
     def encode_all(image):
         """encode_posterior's (mu, ls) and q(y | x) in float64, from ONE pass of the encoder"""
-        if isinstance(model, VariationalAutoEncoder):
+        if family == "shot":
             mu, ls, la = model.encode(image)
             return mu.float().contiguous(), ls.float().contiguous(), torch.exp(la.double())
-        if not image.is_cuda:
-            raise L.ShotVaeHipError("evaluate_aggregate: input is not on an MI355X (no CPU fallback)")
         with torch.no_grad():
             mean, logvar, alpha = model.encode(image)
             return mean.float().contiguous(), (0.5 * logvar.float()).contiguous(), alpha.double()

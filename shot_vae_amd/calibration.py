@@ -23,7 +23,7 @@ import torch
 
 from . import _lib as L
 from .aggregate import partials
-from .neighbors import _p, _st
+from ._latent import _p, _st, eval_only, on_device, regroup, split_batch, vectors
 
 KINDS = {"logit": L.CAL_LOGIT, "prob": L.CAL_PROB}
 MAX_BINS = 1024               # sv_calib_accum: the histogram of a block lives in LDS
@@ -53,9 +53,7 @@ def _posterior(what, x, label, need_label=False, classes=None):
             raise ValueError("%s: the labels are required" % what)
     elif not torch.is_tensor(label) or label.is_floating_point() or label.numel() != x.shape[0]:
         raise ValueError("%s: label must be an integer vector [%d]" % (what, x.shape[0]))
-    for t in (x, label):
-        if torch.is_tensor(t) and not t.is_cuda:
-            raise L.ShotVaeHipError("%s: input is not on an MI355X (no CPU fallback)" % what)
+    on_device(what, x, label)
     return x.detach().float().contiguous(), (label.reshape(-1).long().contiguous() if label is not None else None)
 
 
@@ -252,29 +250,14 @@ class TemperatureScaler:
         return self
 
 
-def _vectors(what, *tensors):
-    """non-empty vectors of one length (a None among them is skipped); the shape checks come first, then the no-CPU rule"""
-    n = None
-    for t in tensors:
-        if t is None:
-            continue
-        if not torch.is_tensor(t) or t.dim() != 1 or t.numel() < 1 or (n is not None and t.numel() != n):
-            raise ValueError("%s: non-empty vectors%s" % (what, "" if n is None else " of one length [%d]" % n))
-        n = t.numel()
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise L.ShotVaeHipError("%s: input is not on an MI355X (no CPU fallback)" % what)
-    return [None if t is None else t.detach() for t in tensors]
-
-
 def rank_counts(q, g, weight=None):
     """-> (greater, equal) int64 [len(q)] on the device: the (weighted) number of values of g above, and equal to, every q[i]
     (sv_rank_scan: exact, the [len(q), len(g)] matrix is never stored).  weight: int64 [len(g)], non-negative -- a MASK keeps every
     shape independent of the data.  A NaN on either side counts nowhere; -0 == 0.  No host synchronisation."""
     if torch.is_tensor(weight) and weight.is_floating_point():
         raise ValueError("rank_counts: weight must be an integer vector")
-    g, weight = _vectors("rank_counts (g, weight)", g, weight)
-    q, g = _vectors("rank_counts (q)", q)[0].float().contiguous(), g.float().contiguous()
+    g, weight = vectors("rank_counts (g, weight)", g, weight)
+    q, g = vectors("rank_counts (q)", q)[0].float().contiguous(), g.float().contiguous()
     if weight is not None:
         weight = weight.long().contiguous()
     Q, N = q.numel(), g.numel()
@@ -298,7 +281,7 @@ def detection_metrics(score, positive, tpr=0.95):
     without a negative row the ratios are NaN."""
     if not 0.0 < float(tpr) <= 1.0:
         raise ValueError("detection_metrics: tpr must be in (0, 1]")
-    score, positive = _vectors("detection_metrics (score, positive)", score, positive)
+    score, positive = vectors("detection_metrics (score, positive)", score, positive)
     score = score.float().contiguous()
     seen = ~torch.isnan(score)
     pos = (positive != 0) & seen
@@ -329,7 +312,7 @@ def selective_metrics(conf, correct):
                 computed from the integers: sum_{i > n - e} (i - (n - e)) / i / n
 
     -> SelectiveResult of float64 device scalars; no host synchronisation.  A NaN confidence ranks nowhere (and its own risk is NaN)."""
-    conf, correct = _vectors("selective_metrics (conf, correct)", conf, correct)
+    conf, correct = vectors("selective_metrics (conf, correct)", conf, correct)
     conf = conf.float().contiguous()
     wrong = (correct == 0).long()
     g, e = rank_counts(conf, conf)
@@ -358,34 +341,6 @@ def _family(what, model):
     raise TypeError("%s: a VariationalAutoEncoder, a SmoothVAE or a WideResNetClassifier, not %s" % (what, type(model).__name__))
 
 
-def _eval_mode(what, model):
-    if model.training:
-        raise NotImplementedError("%s is implemented for eval mode only (no noise, no gradients): call model.eval() first" % what)
-
-
-def _regroup(what, batches, rows):
-    """the (image, label) batches as they come (rows = None), or regrouped into batches of exactly `rows` rows (the last one smaller)"""
-    held, n = [], 0
-    for batch in batches:
-        if not isinstance(batch, (tuple, list)) or len(batch) < 2:
-            raise ValueError("%s: batches must yield (image, label) batches" % what)
-        image, label = batch[0], batch[1]
-        for t in (image, label):
-            if torch.is_tensor(t) and not t.is_cuda:
-                raise L.ShotVaeHipError("%s: input is not on an MI355X (no CPU fallback)" % what)
-        if rows is None:
-            yield image, label
-            continue
-        held.append((image, label.reshape(-1)))
-        n += image.shape[0]
-        while n >= rows:
-            image, label = (torch.cat([h[i] for h in held]) if len(held) > 1 else held[0][i] for i in (0, 1))
-            yield image[:rows], label[:rows]
-            held, n = ([(image[rows:], label[rows:])] if n > rows else []), n - rows
-    if n:
-        yield tuple(torch.cat([h[i] for h in held]) if len(held) > 1 else held[0][i] for i in (0, 1))
-
-
 def evaluate_calibration(model, batches, bins=15, adaptive=False, temperature=None, chunk_rows=256):
     """The calibration of `model`'s class posterior over `batches` ((image, label) batches on the device): SHOT-VAE's log_alpha
     (encode), a smooth-ELBO model's alpha (classify) or the classifier's logits -> Reliability(...).result(adaptive) of all rows, under
@@ -393,11 +348,11 @@ def evaluate_calibration(model, batches, bins=15, adaptive=False, temperature=No
     encoders' last bits depend on the batch size): the result does not depend on how the caller batched the set, only on the order of
     its rows.  chunk_rows=None takes the batches as they come.  One host read at the end."""
     _, posterior = _family("evaluate_calibration", model)
-    _eval_mode("evaluate_calibration", model)
+    eval_only("evaluate_calibration", model)
     if chunk_rows is not None and int(chunk_rows) < 1:
         raise ValueError("evaluate_calibration: chunk_rows must be >= 1 or None")
     rel = None
-    for image, label in _regroup("evaluate_calibration", batches, None if chunk_rows is None else int(chunk_rows)):
+    for image, label in regroup("evaluate_calibration", batches, None if chunk_rows is None else int(chunk_rows)):
         x, kind = posterior(image)
         if rel is None:
             rel = Reliability(x.shape[1], bins=bins)
@@ -437,14 +392,12 @@ def evaluate_detection(model, in_batches, out_batches, score="msp", criterion=No
             raise ValueError("evaluate_detection: score %r needs the criterion (its reconstruction mode and x_sigma)" % score)
     elif criterion is not None or score_args:
         raise ValueError("evaluate_detection: score %r takes no criterion and no score arguments" % score)
-    _eval_mode("evaluate_detection", model)
+    eval_only("evaluate_detection", model)
     values, positive = [], []
     for flag, batches in ((1, in_batches), (0, out_batches)):
         seen = 0
         for batch in batches:
-            image = batch[0] if isinstance(batch, (tuple, list)) else batch
-            if torch.is_tensor(image) and not image.is_cuda:
-                raise L.ShotVaeHipError("evaluate_detection: input is not on an MI355X (no CPU fallback)")
+            image = split_batch("evaluate_detection", batch, None)[0]
             if score in ("elbo", "log_px"):
                 args = dict(score_args)
                 if "row0" not in args and args.get("key") is not None:

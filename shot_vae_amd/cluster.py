@@ -17,13 +17,11 @@ import torch
 
 from . import _lib as L
 from .aggregate import partials
-from .neighbors import _p, _st, encode_posterior
+from ._latent import (LDS_PER_CU, _p, _st, eval_only, gather_codes, latent_family, matrix, num_classes, on_device, resident_partials,
+                      split_batch, take_args)
 
 MAX_CLUSTERS = 1024           # sv_kmeans_accum keeps [K][slice] doubles in LDS
 MAX_CELLS = 1 << 20           # sv_contingency
-
-
-COMPUTE_UNITS, LDS_PER_CU = 256, 160 * 1024          # an MI355X
 
 
 def _slice(k):
@@ -34,27 +32,18 @@ def _slice(k):
 def _partials(k, dim, n):
     """P of sv_kmeans_accum for n rows: aggregate.partials' rule over its grid of ceil(dim / slice) + 1 blocks per state -- every block
     weighed by the share of a compute unit its LDS takes (a quarter at the least: the four blocks per CU that rule aims at) --, lowered
-    until the grid is resident at once: a block walks its rows one after the other, and a second round of blocks would double the
-    time.  A function of the shapes alone."""
+    until the grid is resident at once (resident_partials).  A function of the shapes alone."""
     blocks = -(-dim // _slice(k)) + 1
     per_cu = max(1, min(4, LDS_PER_CU // (k * _slice(k) * 8)))
-    p = partials(blocks * 4 // per_cu, n)
-    while p > 1 and p * blocks > COMPUTE_UNITS * per_cu:
-        p -= 1
-    return p
+    return resident_partials(partials(blocks * 4 // per_cu, n), blocks, per_cu)
 
 
 def _matrix(what, x, dim=None, k=None):
-    """x as a contiguous fp32 device matrix [n, d]; the shape checks come first (they need no device), then the no-CPU rule"""
-    if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError("%s: x must be a non-empty matrix [n, d]" % what)
-    if dim is not None and x.shape[1] != dim:
-        raise ValueError("%s: x has %d columns, the clusterer %d" % (what, x.shape[1], dim))
-    if k is not None and not 1 <= k <= x.shape[0]:
-        raise ValueError("%s: k = %d centroids from %d rows (k > N or k < 1)" % (what, k, x.shape[0]))
-    if not x.is_cuda:
-        raise L.ShotVaeHipError("%s: input is not on an MI355X (no CPU fallback)" % what)
-    return x.detach().float().contiguous()
+    """_latent.matrix for the clusterer; k: that many centroids are to be drawn from the rows"""
+    def limit(n):
+        if k is not None and not 1 <= k <= n:
+            raise ValueError("%s: k = %d centroids from %d rows (k > N or k < 1)" % (what, k, n))
+    return matrix(what, x, dim, "the clusterer", limit)
 
 
 def _assign(x, c, want_dist=True):
@@ -200,9 +189,7 @@ class KMeans:
 def contingency(a, b, ka, kb):
     """-> int64 [ka, kb] on the device: [i, j] = the number of rows with a == i and b == j (a, b: int64 label vectors of one length on
     the device; a row with either label out of range is in no cell).  sv_contingency: integer atomics only, no host synchronisation."""
-    for t in (a, b):
-        if torch.is_tensor(t) and not t.is_cuda:
-            raise L.ShotVaeHipError("contingency: input is not on an MI355X (no CPU fallback)")
+    on_device("contingency", a, b)
     if not torch.is_tensor(a) or not torch.is_tensor(b) or a.dtype != torch.int64 or b.dtype != torch.int64 or a.dim() != 1 \
             or a.shape != b.shape or a.numel() < 1:
         raise ValueError("contingency: a and b must be non-empty int64 vectors of one length")
@@ -331,44 +318,29 @@ def evaluate_clustering(model, data, method="posterior", k=None, space="mu", **k
     clustered: the result does not depend on the batching.  -> partition_metrics of the contingency table (classes x clusters), plus
     `counts` (int64 numpy [k]: the size of every cluster) and `clusters` (int64 [n] on the device: the cluster of every image, in order).
     One host read at the end (k-means with a tolerance adds its convergence checks)."""
-    from .smooth import SmoothVAE
-    from .vae import VariationalAutoEncoder
-    if not isinstance(model, (VariationalAutoEncoder, SmoothVAE)):
-        raise TypeError("evaluate_clustering: a VariationalAutoEncoder or a SmoothVAE, not %s" % type(model).__name__)
+    latent_family("evaluate_clustering", model)
     if method not in ("posterior", "kmeans"):
         raise ValueError("evaluate_clustering: method must be 'posterior' or 'kmeans'")
     if space != "mu":
         raise ValueError("evaluate_clustering: space must be 'mu'")
     if method == "posterior" and (k is not None or kmeans_args):
         raise ValueError("evaluate_clustering: method='posterior' takes no k and no k-means arguments (k is the size of the discrete code)")
-    if model.training:
-        raise NotImplementedError("evaluate_clustering is implemented for eval mode only (no noise, no gradients): call model.eval() first")
-    fit_args = {name: kmeans_args.pop(name) for name in ("max_iter", "tol", "check_every", "n_init") if name in kmeans_args}
+    eval_only("evaluate_clustering", model)
+    fit_args = take_args(kmeans_args, ("max_iter", "tol", "check_every", "n_init"))
+    classes = num_classes(model)
 
-    rows, labels, classes = [], [], None
-    for batch in data:
-        if not isinstance(batch, (tuple, list)) or len(batch) < 2:
-            raise ValueError("evaluate_clustering: data must yield (image, label) batches")
-        image, label = batch[0], batch[1]
-        for t in (image, label):
-            if torch.is_tensor(t) and not t.is_cuda:
-                raise L.ShotVaeHipError("evaluate_clustering: input is not on an MI355X (no CPU fallback)")
-        label = label.reshape(-1).long()
-        if label.numel() != image.shape[0]:
-            raise ValueError("evaluate_clustering: %d labels for %d images" % (label.numel(), image.shape[0]))
-        if method == "posterior" or classes is None:
-            with torch.no_grad():
-                qy = model.encode(image)[2]            # log alpha (SHOT-VAE) or alpha (smooth): the same first maximum
-            classes = qy.shape[1]
-        rows.append(qy.argmax(dim=1) if method == "posterior" else encode_posterior(model, image)[0])
-        labels.append(label)
-    if not rows:
-        raise ValueError("evaluate_clustering: the dataset is empty")
-    label = torch.cat(labels)
     if method == "posterior":
-        k, cluster = classes, torch.cat(rows)
+        rows, labels = [], []
+        for batch in data:
+            image, label = split_batch("evaluate_clustering", batch, True)
+            with torch.no_grad():
+                rows.append(model.encode(image)[2].argmax(dim=1))      # log alpha (SHOT-VAE) or alpha (smooth): the same first maximum
+            labels.append(label)
+        if not rows:
+            raise ValueError("evaluate_clustering: the dataset is empty")
+        k, cluster, label = classes, torch.cat(rows), torch.cat(labels)
     else:
-        mu = torch.cat(rows)
+        mu, _, label = gather_codes("evaluate_clustering", model, data)
         k = classes if k is None else int(k)
         cluster = KMeans(k, mu.shape[1], **kmeans_args).fit(mu, **fit_args).predict(mu)
     table = contingency(label, cluster, classes, k)

@@ -12,8 +12,8 @@ import torch
 
 from . import _lib as L
 from .aggregate import partials
-from .calibration import _regroup
-from .neighbors import MAX_K, LatentIndex, _p, _st, encode_posterior
+from ._latent import _p, _st, eval_only, gather_codes, latent_family, num_classes, on_device, take_args
+from .neighbors import MAX_K, LatentIndex
 
 REPULSE_ROWS = 256            # sv_tsne_repulse: rows per block
 
@@ -27,12 +27,6 @@ def repulse_partials(n):
 def update_scratch(n):
     """the number of doubles sv_tsne_update needs as scratch for n points"""
     return 3 * (-(-n // 256))
-
-
-def _device(what, *tensors):
-    for t in tensors:
-        if torch.is_tensor(t) and not t.is_cuda:
-            raise L.ShotVaeHipError("%s: input is not on an MI355X (no CPU fallback)" % what)
 
 
 def conditional_affinities(dist, idx, perplexity, tol=1e-5, max_steps=100):
@@ -52,7 +46,7 @@ def conditional_affinities(dist, idx, perplexity, tol=1e-5, max_steps=100):
         raise ValueError("conditional_affinities: perplexity must be in (1, k = %d); got %g" % (k, perplexity))
     if tol < 0 or max_steps < 1:
         raise ValueError("conditional_affinities: tol >= 0 and max_steps >= 1")
-    _device("conditional_affinities", dist, idx)
+    on_device("conditional_affinities", dist, idx)
     dist, idx = dist.detach().float().contiguous(), idx.contiguous()
     p = torch.empty_like(dist)
     beta = torch.empty(n, dtype=torch.float64, device=dist.device)
@@ -143,7 +137,7 @@ class TSNE:
         if torch.is_tensor(init):
             if init.dim() != 2 or init.shape[1] != self.n_components:
                 raise ValueError("TSNE: init must be a tensor [N, %d]" % self.n_components)
-            _device("TSNE", init)
+            on_device("TSNE", init)
         elif init not in ("pca", "random"):
             raise ValueError("TSNE: init must be 'pca', 'random' or a tensor [N, n_components]")
         self.init = init
@@ -162,7 +156,7 @@ class TSNE:
             raise ValueError("TSNE: perplexity = %g must be below k = %d (N = %d)" % (self.perplexity, k, n))
         if torch.is_tensor(self.init) and self.init.shape[0] != n:
             raise ValueError("TSNE: init has %d rows, the data %d" % (self.init.shape[0], n))
-        _device("TSNE", mu, ls)
+        on_device("TSNE", mu, ls)
         dev = mu.device
         index = LatentIndex(mu.shape[1], self.metric)
         index.add(mu, ls)
@@ -254,35 +248,18 @@ def evaluate_embedding(model, data, k=10, chunk_rows=256, **tsne_args):
         kl, n_iter                  TSNE's kl_divergence_ and n_iter_
         neighbourhood_hit           the leave-one-out k-NN label accuracy IN THE EMBEDDING (LatentIndex("euclid"), sv_knn_vote)
         neighbourhood_preservation  the mean share of a row's k latent neighbours (TSNE's metric) found among its k embedded neighbours"""
-    from .smooth import SmoothVAE
-    from .vae import VariationalAutoEncoder
-    if not isinstance(model, (VariationalAutoEncoder, SmoothVAE)):
-        raise TypeError("evaluate_embedding: a VariationalAutoEncoder or a SmoothVAE, not %s" % type(model).__name__)
-    if model.training:
-        raise NotImplementedError("evaluate_embedding is implemented for eval mode only (no noise, no gradients): call model.eval() first")
+    latent_family("evaluate_embedding", model)
+    eval_only("evaluate_embedding", model)
     k = int(k)
     if not 1 <= k <= MAX_K:
         raise ValueError("evaluate_embedding: k must be in [1, %d]" % MAX_K)
     if chunk_rows is not None and int(chunk_rows) < 1:
         raise ValueError("evaluate_embedding: chunk_rows must be >= 1 or None")
-    fit_args = {name: tsne_args.pop(name) for name in ("check_every", "min_grad_norm") if name in tsne_args}
+    fit_args = take_args(tsne_args, ("check_every", "min_grad_norm"))
     ts = TSNE(**tsne_args)
 
-    mus, lss, labels, classes = [], [], [], None
-    for image, label in _regroup("evaluate_embedding", data, None if chunk_rows is None else int(chunk_rows)):
-        label = label.reshape(-1).long()
-        if label.numel() != image.shape[0]:
-            raise ValueError("evaluate_embedding: %d labels for %d images" % (label.numel(), image.shape[0]))
-        if classes is None:
-            with torch.no_grad():
-                classes = model.encode(image)[2].shape[1]
-        mu, ls = encode_posterior(model, image)
-        mus.append(mu)
-        lss.append(ls)
-        labels.append(label)
-    if not mus:
-        raise ValueError("evaluate_embedding: the dataset is empty")
-    mu, ls, label = torch.cat(mus), torch.cat(lss), torch.cat(labels)
+    classes = num_classes(model)
+    mu, ls, label = gather_codes("evaluate_embedding", model, data, chunk_rows=chunk_rows)
     n = mu.shape[0]
     if k > n - 1:
         raise ValueError("evaluate_embedding: k = %d neighbours from %d rows" % (k, n))

@@ -177,8 +177,8 @@ def evaluate_knn(model, gallery_batches, test_batches, k=20, metric="kl", weight
     are the gallery, every image of `test_batches` votes among its k nearest under `metric` -> KnnEvaluator.result(): accuracy,
     correct, total, per_class_accuracy, confusion.  num_classes defaults to the model's number of classes.  The model must be in eval
     mode (encode_posterior).  Integer counts: the result does not depend on how either set is batched."""
-    from .neighbors import LatentIndex, encode_posterior, _metric
-    _metric(metric)                                                      # an unknown metric fails before any encoding
+    from .neighbors import LatentIndex, encode_posterior, metric_code
+    metric_code(metric)                                                     # an unknown metric fails before any encoding
     if num_classes is None:
         num_classes = model.latent_disc_dim if hasattr(model, "latent_disc_dim") else model._plan.K
     index = None

@@ -18,8 +18,8 @@ import torch
 
 from . import _lib as L
 from .aggregate import partials
-from .cluster import COMPUTE_UNITS, KMeans, _partials as _kmeans_partials, contingency, partition_metrics
-from .neighbors import _p, _st, encode_posterior
+from ._latent import _p, _st, eval_only, gather_codes, latent_family, matrix, num_classes, on_device, resident_partials, take_args
+from .cluster import KMeans, _partials as _kmeans_partials, contingency, partition_metrics
 
 MAX_DIM = 1 << 20             # sv_gmm_accum: a block owns 32 dimensions, the grid's second dimension holds 65535 blocks
 SLICE = 32
@@ -34,26 +34,17 @@ def n_parameters(k, dim):
 
 def _partials(k, dim, n):
     """P of sv_gmm_accum for n rows: aggregate.partials' rule over its grid of ceil(k / tile) x ceil(dim / 32) blocks per state (tile = 16
-    components for k <= 16, else 64), lowered until the grid is resident at once -- a block walks its rows one after the other, and a
-    second round of blocks would double the time.  A function of the shapes alone."""
+    components for k <= 16, else 64), lowered until the grid is resident at once (resident_partials).  A function of the shapes alone."""
     blocks = (1 if k <= 16 else -(-k // 64)) * -(-dim // SLICE)
-    p = partials(blocks, n)
-    while p > 1 and p * blocks > COMPUTE_UNITS * BLOCKS_PER_CU:
-        p -= 1
-    return p
+    return resident_partials(partials(blocks, n), blocks, BLOCKS_PER_CU)
 
 
 def _matrix(what, x, dim=None, k=None):
-    """x as a contiguous fp32 device matrix [n, d]; the shape checks come first (they need no device), then the no-CPU rule"""
-    if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError("%s: x must be a non-empty matrix [n, d]" % what)
-    if dim is not None and x.shape[1] != dim:
-        raise ValueError("%s: x has %d columns, the mixture %d" % (what, x.shape[1], dim))
-    if k is not None and k > x.shape[0]:
-        raise ValueError("%s: k = %d components from %d rows (k > N)" % (what, k, x.shape[0]))
-    if not x.is_cuda:
-        raise L.ShotVaeHipError("%s: input is not on an MI355X (no CPU fallback)" % what)
-    return x.detach().float().contiguous()
+    """_latent.matrix for the mixture; k: that many components are to be seeded from the rows"""
+    def limit(n):
+        if k is not None and k > n:
+            raise ValueError("%s: k = %d components from %d rows (k > N)" % (what, k, n))
+    return matrix(what, x, dim, "the mixture", limit)
 
 
 def _key_tensor(what, key, device):
@@ -124,9 +115,7 @@ class GaussianMixture:
         for t, shape in shapes:
             if not torch.is_tensor(t) or tuple(t.shape) != shape:
                 raise ValueError("GaussianMixture.set_parameters: weights [%d], means and variances [%d, %d]" % (self.k, self.k, self.dim))
-        for t, _ in shapes:
-            if not t.is_cuda:
-                raise L.ShotVaeHipError("GaussianMixture.set_parameters: input is not on an MI355X (no CPU fallback)")
+        on_device("GaussianMixture.set_parameters", weights, means, variances)
         self.logw = weights.detach().double().log().float().contiguous()
         self.mean = means.detach().float().contiguous().clone()
         self.var = variances.detach().float().contiguous().clone()
@@ -322,27 +311,6 @@ class GaussianMixture:
         return self
 
 
-def _gather(what, model, batches, classes):
-    """-> (posterior means of all rows [n, d], labels int64 [n] or None when a batch carries none)"""
-    rows, labels, labelled = [], [], True
-    for batch in batches:
-        image, label = (batch[0], batch[1] if len(batch) > 1 else None) if isinstance(batch, (tuple, list)) else (batch, None)
-        for t in (image, label):
-            if torch.is_tensor(t) and not t.is_cuda:
-                raise L.ShotVaeHipError("%s: input is not on an MI355X (no CPU fallback)" % what)
-        rows.append(encode_posterior(model, image)[0])
-        if label is None:
-            labelled = False
-        else:
-            label = label.reshape(-1).long()
-            if label.numel() != image.shape[0]:
-                raise ValueError("%s: %d labels for %d images" % (what, label.numel(), image.shape[0]))
-            labels.append(label)
-    if not rows:
-        raise ValueError("%s: the dataset is empty" % what)
-    return torch.cat(rows), (torch.cat(labels) if labelled else None)
-
-
 def evaluate_mixture(model, fit_batches, test_batches=None, k=10, space="mu", **fit_args):
     """How much better than the prior does a mixture of k diagonal Gaussians describe the codes of `model` (a VariationalAutoEncoder or a
     SmoothVAE, in eval mode: NotImplementedError otherwise, as for score)?  fit_batches / test_batches: (image, label) or (image,) tuples,
@@ -358,21 +326,19 @@ def evaluate_mixture(model, fit_batches, test_batches=None, k=10, space="mu", **
         mixture                      the fitted GaussianMixture
 
     One host read at the end beyond those of fit."""
-    from .smooth import SmoothVAE
-    from .vae import VariationalAutoEncoder
-    if not isinstance(model, (VariationalAutoEncoder, SmoothVAE)):
-        raise TypeError("evaluate_mixture: a VariationalAutoEncoder or a SmoothVAE, not %s" % type(model).__name__)
+    latent_family("evaluate_mixture", model)
     if space != "mu":
         raise ValueError("evaluate_mixture: space must be 'mu'")
-    if model.training:
-        raise NotImplementedError("evaluate_mixture is implemented for eval mode only (no noise, no gradients): call model.eval() first")
-    run_args = {name: fit_args.pop(name) for name in ("max_iter", "tol", "check_every", "n_init") if name in fit_args}
-    classes = model._plan.K if isinstance(model, VariationalAutoEncoder) else model.latent_disc_dim
+    eval_only("evaluate_mixture", model)
+    run_args = take_args(fit_args, ("max_iter", "tol", "check_every", "n_init"))
+    classes = num_classes(model)
     k = int(k)
 
-    sets = [_gather("evaluate_mixture", model, fit_batches, classes)]
-    if test_batches is not None:
-        sets.append(_gather("evaluate_mixture", model, test_batches, classes))
+    def codes(batches):
+        mu, _, label = gather_codes("evaluate_mixture", model, batches, need_label=False)
+        return mu, label
+
+    sets = [codes(fit_batches)] + ([codes(test_batches)] if test_batches is not None else [])
     dim = sets[0][0].shape[1]
     gm = GaussianMixture(k, dim, **fit_args).fit(sets[0][0], **run_args)
     packed, tables = [], []
@@ -404,19 +370,15 @@ def generate_from_mixture(model, mixture, labels, key, row0=0, **decode_args):
     key, row0), then model.decode(z, labels, **decode_args) (a VariationalAutoEncoder; sigmoid=True unless said otherwise: the images
     generate() gives) or model.decode([z | one-hot(labels)]) (a SmoothVAE; a label outside the code sets no class).  A row depends only
     on (key, row0 + its row), as in generate()."""
-    from .smooth import SmoothVAE
-    from .vae import VariationalAutoEncoder
-    if not isinstance(model, (VariationalAutoEncoder, SmoothVAE)):
-        raise TypeError("generate_from_mixture: a VariationalAutoEncoder or a SmoothVAE, not %s" % type(model).__name__)
+    family = latent_family("generate_from_mixture", model)
     if not isinstance(mixture, GaussianMixture):
         raise TypeError("generate_from_mixture: a GaussianMixture, not %s" % type(mixture).__name__)
     if not torch.is_tensor(labels) or labels.dtype != torch.int64 or labels.numel() < 1:
         raise ValueError("generate_from_mixture: labels must be a non-empty int64 vector on the device")
-    if not labels.is_cuda:
-        raise L.ShotVaeHipError("generate_from_mixture: input is not on an MI355X (no CPU fallback)")
+    on_device("generate_from_mixture", labels)
     labels = labels.reshape(-1).contiguous()
     z = mixture.sample(labels.numel(), key, row0=row0)
-    if isinstance(model, VariationalAutoEncoder):
+    if family == "shot":
         if mixture.dim != model._plan.ldc:
             raise ValueError("generate_from_mixture: the mixture has %d dimensions, the model's code %d" % (mixture.dim, model._plan.ldc))
         decode_args.setdefault("sigmoid", True)

@@ -11,26 +11,17 @@ k-nearest-neighbour search / classification in latent space, on the HIP path (cs
 
 `ls` is LOG SIGMA everywhere (the SHOT-VAE convention; encode_posterior halves a smooth model's logvar).  The fused search never
 stores the [queries, gallery] matrix; nothing here synchronises with the host, and there is no CPU fallback."""
-import ctypes as C
-
 import torch
 
 from . import _lib as L
+from ._latent import _p, _st, eval_only, latent_family, on_device
 
 METRICS = {"kl": L.DIST_KL, "w2": L.DIST_W2, "wasserstein": L.DIST_W2, "euclid": L.DIST_EUCLID, "euclidean": L.DIST_EUCLID,
            "cosine": L.DIST_COSINE}
 MAX_K = 256
 
 
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _metric(metric):
+def metric_code(metric):
     if metric not in METRICS:
         raise ValueError("unknown metric %r (one of %s)" % (metric, ", ".join(sorted(METRICS))))
     return METRICS[metric]
@@ -40,11 +31,9 @@ def _reads_ls(code):
     return code in (L.DIST_KL, L.DIST_W2)
 
 
-def _rows(what, code, mu, ls, dim=None):
+def posterior_rows(what, code, mu, ls, dim=None):
     """(mu, ls) as contiguous fp32 device matrices [n, d]; ls = None where the metric does not read it"""
-    for t in (mu, ls):
-        if torch.is_tensor(t) and not t.is_cuda:
-            raise L.ShotVaeHipError("%s: input is not on an MI355X (no CPU fallback)" % what)
+    on_device(what, mu, ls)
     if not torch.is_tensor(mu) or mu.dim() != 2 or mu.shape[0] < 1 or mu.shape[1] < 1:
         raise ValueError("%s: mu must be a non-empty matrix [n, d]" % what)
     if dim is not None and mu.shape[1] != dim:
@@ -61,9 +50,9 @@ def pairwise_distance(mu1, ls1, mu2, ls2=None, metric="kl"):
     """The [n1, n2] fp32 matrix of `metric` between the posteriors (mu1, ls1) and (mu2, ls2), the first argument first:
     "kl" KL(N_1 || N_2), "w2" the squared 2-Wasserstein distance, "euclid" the squared distance of the means, "cosine" the reference's
     mu1 . mu2 / (|mu1|^2 |mu2|^2) (a similarity).  The last two ignore ls (pass None)."""
-    code = _metric(metric)
-    mu1, ls1 = _rows("pairwise_distance", code, mu1, ls1)
-    mu2, ls2 = _rows("pairwise_distance", code, mu2, ls2, dim=mu1.shape[1])
+    code = metric_code(metric)
+    mu1, ls1 = posterior_rows("pairwise_distance", code, mu1, ls1)
+    mu2, ls2 = posterior_rows("pairwise_distance", code, mu2, ls2, dim=mu1.shape[1])
     out = torch.empty(mu1.shape[0], mu2.shape[0], dtype=torch.float32, device=mu1.device)
     L.call("sv_pairdist", code, _p(mu1), _p(ls1), mu1.shape[0], _p(mu2), _p(ls2), mu2.shape[0], mu1.shape[1], _p(out), out.shape[1],
            _st())
@@ -98,21 +87,14 @@ def calculate_mean_dist_pairwise(u1, u2, GPU_flag=True, distance="euclidean"):
 def encode_posterior(model, x):
     """(mu, log_sigma), fp32 [B, d] each, of the images x under `model`: a VariationalAutoEncoder's encode(), or a SmoothVAE's
     encode() with log_sigma = logvar / 2.  Eval mode only, as every inference call; no gradients."""
-    from .smooth import SmoothVAE
-    from .vae import VariationalAutoEncoder
-    if isinstance(model, VariationalAutoEncoder):
+    if latent_family("encode_posterior", model) == "shot":
         mu, ls = model.encode(x)[:2]
         return mu.float().contiguous(), ls.float().contiguous()
-    if isinstance(model, SmoothVAE):
-        if model.training:
-            raise NotImplementedError("encode_posterior is implemented for eval mode only (no noise, no gradients): call "
-                                      "model.eval() first")
-        if not x.is_cuda:
-            raise L.ShotVaeHipError("encode_posterior: input is not on an MI355X (no CPU fallback)")
-        with torch.no_grad():
-            mean, logvar = model.encode(x)[:2]
-            return mean.float().contiguous(), (0.5 * logvar.float()).contiguous()
-    raise TypeError("encode_posterior: a VariationalAutoEncoder or a SmoothVAE, not %s" % type(model).__name__)
+    eval_only("encode_posterior", model)
+    on_device("encode_posterior", x)
+    with torch.no_grad():
+        mean, logvar = model.encode(x)[:2]
+        return mean.float().contiguous(), (0.5 * logvar.float()).contiguous()
 
 
 class LatentIndex:
@@ -123,7 +105,7 @@ class LatentIndex:
     synchronisation and, once the gallery is fixed, can be captured under torch.cuda.graph and replayed on new queries."""
 
     def __init__(self, dim, metric="kl", num_classes=None):
-        self.dim, self.metric, self.code = int(dim), metric, _metric(metric)
+        self.dim, self.metric, self.code = int(dim), metric, metric_code(metric)
         if self.dim < 1:
             raise ValueError("LatentIndex: dim must be >= 1")
         self.num_classes = None if num_classes is None else int(num_classes)
@@ -151,7 +133,7 @@ class LatentIndex:
     def add(self, mu, ls=None, labels=None):
         """appends the rows (mu, ls) [n, dim] (ls may be None for "euclid" / "cosine") with their int64 labels [n] (None: unlabelled,
         such rows are found by search and cast no vote in classify); returns the global index of the first row added"""
-        mu, ls = _rows("LatentIndex.add", self.code, mu, ls, dim=self.dim)
+        mu, ls = posterior_rows("LatentIndex.add", self.code, mu, ls, dim=self.dim)
         n = mu.shape[0]
         if labels is not None:
             if not torch.is_tensor(labels) or labels.numel() != n:
@@ -178,7 +160,7 @@ class LatentIndex:
         index; slots beyond the gallery's size are idx = -1, dist = +inf (-inf under "cosine", whose values are similarities).
         exclude_self_from = s: query i is gallery row s + i and is left out of its own list (leave-one-out)."""
         k = self._check_k(k)
-        mu, ls = _rows("LatentIndex.search", self.code, mu, ls, dim=self.dim)
+        mu, ls = posterior_rows("LatentIndex.search", self.code, mu, ls, dim=self.dim)
         if self.n == 0:
             raise ValueError("LatentIndex.search: the index is empty")
         Q = mu.shape[0]
@@ -201,9 +183,7 @@ class LatentIndex:
         if self.num_classes is None:
             raise ValueError("LatentIndex.classify: the index was built without num_classes")
         K = self.num_classes
-        for t in (label, counts, confusion):
-            if torch.is_tensor(t) and not t.is_cuda:
-                raise L.ShotVaeHipError("LatentIndex.classify: input is not on an MI355X (no CPU fallback)")
+        on_device("LatentIndex.classify", label, counts, confusion)
         val, idx = self.search(mu, ls, k)
         Q = val.shape[0]
         if label is not None:

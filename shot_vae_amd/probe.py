@@ -18,8 +18,8 @@ import torch
 
 from . import _lib as L
 from .aggregate import partials
-from .cluster import COMPUTE_UNITS
-from .neighbors import _p, _st, encode_posterior
+from ._latent import (_p, _st, eval_only, gather_codes, label_budgets, labels as _labels, latent_family, matrix, num_classes,
+                      resident_partials, take_args)
 
 MAX_DIM = 1 << 20             # sv_probe_accum: a block owns 32 dimensions, the grid's second dimension holds 65535 blocks
 SLICE = 32
@@ -30,30 +30,11 @@ def _partials(k, dim, n):
     """P of sv_probe_accum for n rows: mixture._partials' rule over this kernel's grid of ceil(k / tile) x ceil(dim / 32) blocks per state
     (tile = 16 classes for k <= 16, else 64), lowered until the grid is resident at once.  A function of the shapes alone."""
     blocks = (1 if k <= 16 else -(-k // 64)) * -(-dim // SLICE)
-    p = partials(blocks, n)
-    while p > 1 and p * blocks > COMPUTE_UNITS * BLOCKS_PER_CU:
-        p -= 1
-    return p
+    return resident_partials(partials(blocks, n), blocks, BLOCKS_PER_CU)
 
 
 def _matrix(what, x, dim=None):
-    """x as a contiguous fp32 device matrix [n, d]; the shape checks come first (they need no device), then the no-CPU rule"""
-    if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError("%s: x must be a non-empty matrix [n, d]" % what)
-    if dim is not None and x.shape[1] != dim:
-        raise ValueError("%s: x has %d columns, the probe %d" % (what, x.shape[1], dim))
-    if not x.is_cuda:
-        raise L.ShotVaeHipError("%s: input is not on an MI355X (no CPU fallback)" % what)
-    return x.detach().float().contiguous()
-
-
-def _labels(what, y, n):
-    """y as a contiguous int64 device vector [n]"""
-    if not torch.is_tensor(y) or y.dim() != 1 or y.shape[0] != n or y.dtype.is_floating_point or y.dtype == torch.bool:
-        raise ValueError("%s: y must be an integer vector [%d]" % (what, n))
-    if not y.is_cuda:
-        raise L.ShotVaeHipError("%s: labels are not on an MI355X (no CPU fallback)" % what)
-    return y.detach().long().contiguous()
+    return matrix(what, x, dim, "the probe")
 
 
 def _probe_loop(step, read, max_iter, tol, check_every):
@@ -317,26 +298,6 @@ class LinearProbe:
         return self
 
 
-def _gather(what, model, batches, space):
-    """-> (the rows of all batches [n, d], labels int64 [n])"""
-    rows, labels = [], []
-    for batch in batches:
-        if not isinstance(batch, (tuple, list)) or len(batch) < 2:
-            raise ValueError("%s: the batches must be (image, label) tuples" % what)
-        image, label = batch[0], batch[1]
-        for t in (image, label):
-            if torch.is_tensor(t) and not t.is_cuda:
-                raise L.ShotVaeHipError("%s: input is not on an MI355X (no CPU fallback)" % what)
-        rows.append(encode_posterior(model, image)[0] if space == "mu" else model.features(image).float().contiguous())
-        label = label.reshape(-1).long()
-        if label.numel() != image.shape[0]:
-            raise ValueError("%s: %d labels for %d images" % (what, label.numel(), image.shape[0]))
-        labels.append(label)
-    if not rows:
-        raise ValueError("%s: the dataset is empty" % what)
-    return torch.cat(rows), torch.cat(labels)
-
-
 def evaluate_probe(model, fit_batches, test_batches, space="mu", labels_per_class=None, seed=0, **probe_args):
     """The linear evaluation protocol on the codes of `model` (a VariationalAutoEncoder or a SmoothVAE, in eval mode: NotImplementedError
     otherwise, as for score): a LinearProbe(classes, d, **probe_args: C, standardize, and fit's max_iter, tol, check_every) is fitted to
@@ -351,27 +312,18 @@ def evaluate_probe(model, fit_batches, test_batches, space="mu", labels_per_clas
         n_iter, converged            of the fit;   probe   the fitted LinearProbe
 
     Beyond fit's host reads, one host read per budget."""
-    from .smooth import SmoothVAE
-    from .vae import VariationalAutoEncoder
-    if not isinstance(model, (VariationalAutoEncoder, SmoothVAE)):
-        raise TypeError("evaluate_probe: a VariationalAutoEncoder or a SmoothVAE, not %s" % type(model).__name__)
+    latent_family("evaluate_probe", model)
     if space not in ("mu", "features"):
         raise ValueError("evaluate_probe: space must be 'mu' or 'features'")
     if space == "features" and not hasattr(model, "features"):
         raise ValueError("evaluate_probe: %s has no features(): use space='mu'" % type(model).__name__)
-    if model.training:
-        raise NotImplementedError("evaluate_probe is implemented for eval mode only (no noise, no gradients): call model.eval() first")
-    budgets = list(labels_per_class) if isinstance(labels_per_class, (list, tuple)) else [labels_per_class]
-    for m in budgets:
-        if m is not None and (isinstance(m, bool) or int(m) != m or int(m) < 1):
-            raise ValueError("evaluate_probe: a budget must be None or an integer >= 1, not %r" % (m,))
-    if len(set(budgets)) != len(budgets):
-        raise ValueError("evaluate_probe: a budget is listed twice")
-    run_args = {name: probe_args.pop(name) for name in ("max_iter", "tol", "check_every") if name in probe_args}
-    classes = model._plan.K if isinstance(model, VariationalAutoEncoder) else model.latent_disc_dim
+    eval_only("evaluate_probe", model)
+    budgets = label_budgets("evaluate_probe", labels_per_class)
+    run_args = take_args(probe_args, ("max_iter", "tol", "check_every"))
+    classes = num_classes(model)
 
-    x_fit, y_fit = _gather("evaluate_probe", model, fit_batches, space)
-    x_test, y_test = _gather("evaluate_probe", model, test_batches, space)
+    x_fit, _, y_fit = gather_codes("evaluate_probe", model, fit_batches, space)
+    x_test, _, y_test = gather_codes("evaluate_probe", model, test_batches, space)
     res = {}
     for m in budgets:
         y = y_fit if m is None else select_labels(y_fit, int(m), classes, seed)

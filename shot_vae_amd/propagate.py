@@ -14,10 +14,10 @@ there is no CPU fallback."""
 import torch
 
 from . import _lib as L
-from .calibration import _regroup
-from .embed import _device, conditional_affinities, symmetrize
-from .neighbors import MAX_K, LatentIndex, _p, _st
-from .probe import _labels, select_labels
+from ._latent import _p, _st, eval_only, gather_codes, label_budgets, labels as _labels, latent_family, num_classes, on_device
+from .embed import conditional_affinities, symmetrize
+from .neighbors import MAX_K, LatentIndex
+from .probe import select_labels
 
 MAX_CLASSES = 1024            # sv_lp_step
 VARIANTS = {"spreading": L.LP_SPREADING, "propagation": L.LP_PROPAGATION}
@@ -35,7 +35,7 @@ def _csr(what, rowptr, col, val):
     if not all(torch.is_tensor(t) and t.dim() == 1 for t in (rowptr, col, val)) or rowptr.shape[0] < 2 or col.shape != val.shape \
             or rowptr.dtype != torch.int64 or col.dtype != torch.int64:
         raise ValueError("%s: rowptr int64 [N + 1], col int64 [nnz] and val [nnz]" % what)
-    _device(what, rowptr, col, val)
+    on_device(what, rowptr, col, val)
     return rowptr.contiguous(), col.contiguous(), val.detach().float().contiguous()
 
 
@@ -53,7 +53,7 @@ def knn_graph(mu, ls=None, k=7, metric="kl", weights="connectivity", perplexity=
     k = int(k)
     if not 1 <= k <= min(MAX_K, mu.shape[0] - 1):
         raise ValueError("knn_graph: k must be in [1, min(%d, N - 1 = %d)]; got %d" % (MAX_K, mu.shape[0] - 1, k))
-    _device("knn_graph", mu, ls)
+    on_device("knn_graph", mu, ls)
     index = LatentIndex(mu.shape[1], metric)
     index.add(mu, ls)
     dist, idx = index.search(mu, ls, k=k, exclude_self_from=0)
@@ -235,7 +235,7 @@ class LabelPropagator:
         dim = self.rows[0].shape[1]
         if not torch.is_tensor(mu) or mu.dim() != 2 or mu.shape[0] < 1 or mu.shape[1] != dim:
             raise ValueError("%s: mu must be a matrix [Q >= 1, %d]" % (what, dim))
-        _device(what, mu, ls, self.label_distributions_, *self.rows)
+        on_device(what, mu, ls, self.label_distributions_, *self.rows)
         if self.index is None:
             self.index = LatentIndex(dim, self.metric)
             self.index.add(*self.rows)
@@ -305,53 +305,28 @@ def evaluate_propagation(model, fit_batches, test_batches=None, space="mu", labe
         n_unreached                  the graph's rows no label reached;   n_iter, converged   of the fit;   propagator
 
     Beyond fit's host reads, one host read per budget."""
-    from .neighbors import encode_posterior
-    from .smooth import SmoothVAE
-    from .vae import VariationalAutoEncoder
-    if not isinstance(model, (VariationalAutoEncoder, SmoothVAE)):
-        raise TypeError("evaluate_propagation: a VariationalAutoEncoder or a SmoothVAE, not %s" % type(model).__name__)
+    latent_family("evaluate_propagation", model)
     if space not in ("mu", "features"):
         raise ValueError("evaluate_propagation: space must be 'mu' or 'features'")
     if mode not in ("transductive", "inductive"):
         raise ValueError("evaluate_propagation: mode must be 'transductive' or 'inductive'")
     if space == "features" and not hasattr(model, "features"):
         raise ValueError("evaluate_propagation: %s has no features(): use space='mu'" % type(model).__name__)
-    if model.training:
-        raise NotImplementedError("evaluate_propagation is implemented for eval mode only (no noise, no gradients): call model.eval() first")
+    eval_only("evaluate_propagation", model)
     if chunk_rows is not None and int(chunk_rows) < 1:
         raise ValueError("evaluate_propagation: chunk_rows must be >= 1 or None")
-    budgets = list(labels_per_class) if isinstance(labels_per_class, (list, tuple)) else [labels_per_class]
-    for m in budgets:
-        if m is not None and (isinstance(m, bool) or int(m) != m or int(m) < 1):
-            raise ValueError("evaluate_propagation: a budget must be None or an integer >= 1, not %r" % (m,))
-    if len(set(budgets)) != len(budgets):
-        raise ValueError("evaluate_propagation: a budget is listed twice")
+    budgets = label_budgets("evaluate_propagation", labels_per_class)
     if mode == "inductive" and test_batches is None:
         raise ValueError("evaluate_propagation: mode='inductive' needs test_batches")
     check_every = args.pop("check_every", 10)
     if space == "features":
         args.setdefault("metric", "euclid")
-    classes = model._plan.K if isinstance(model, VariationalAutoEncoder) else model.latent_disc_dim
-    rows = None if chunk_rows is None else int(chunk_rows)
+    classes = num_classes(model)
 
-    def gather(batches):
-        xs, lss, labels = [], [], []
-        for image, label in _regroup("evaluate_propagation", batches, rows):
-            label = label.reshape(-1).long()
-            if label.numel() != image.shape[0]:
-                raise ValueError("evaluate_propagation: %d labels for %d images" % (label.numel(), image.shape[0]))
-            x, ls = encode_posterior(model, image) if space == "mu" else (model.features(image).float().contiguous(), None)
-            xs.append(x)
-            lss.append(ls)
-            labels.append(label)
-        if not xs:
-            raise ValueError("evaluate_propagation: the dataset is empty")
-        return torch.cat(xs), (torch.cat(lss) if space == "mu" else None), torch.cat(labels)
-
-    x_fit, ls_fit, y_fit = gather(fit_batches)
+    x_fit, ls_fit, y_fit = gather_codes("evaluate_propagation", model, fit_batches, space, chunk_rows)
     n_fit = x_fit.shape[0]
     if test_batches is not None:
-        x_test, ls_test, y_test = gather(test_batches)
+        x_test, ls_test, y_test = gather_codes("evaluate_propagation", model, test_batches, space, chunk_rows)
     if args.get("metric", "kl") in ("euclid", "euclidean"):
         ls_fit = ls_test = None
     if mode == "transductive" and test_batches is not None:

@@ -18,14 +18,15 @@ import torch
 
 from . import _lib as L
 from .aggregate import partials
-from .neighbors import LatentIndex, MAX_K, _metric, _p, _rows, _st, encode_posterior
+from ._latent import _p, _st, eval_only, latent_family, on_device, split_batch
+from .neighbors import LatentIndex, MAX_K, encode_posterior, metric_code, posterior_rows
 
 BALL_METRICS = (L.DIST_EUCLID, L.DIST_W2)
 FIT_CHUNK = 8192              # query rows per search of fit(): the lists stay at FIT_CHUNK x k slots
 
 
 def _ball_metric(what, metric):
-    code = _metric(metric)
+    code = metric_code(metric)
     if code not in BALL_METRICS:
         raise ValueError("%s: a k-th-neighbour radius needs a symmetric distance (\"euclid\" or \"w2\"), not %r: KL is not symmetric and "
                          "the cosine is a similarity" % (what, metric))
@@ -87,7 +88,7 @@ class Manifold:
             raise ValueError("Manifold.count: the set has no radii (never fitted, or rows were added since): call fit(k) first")
         if torch.is_tensor(gallery_count) and not gallery_count.is_cuda:
             raise L.ShotVaeHipError("Manifold.count: gallery_count is not on an MI355X (no CPU fallback)")
-        mu, ls = _rows("Manifold.count", self.code, mu, ls, dim=self.dim)
+        mu, ls = posterior_rows("Manifold.count", self.code, mu, ls, dim=self.dim)
         N, Q = len(self.index), mu.shape[0]
         if gallery_count is not None and (not torch.is_tensor(gallery_count) or gallery_count.dtype != torch.int64
                                           or tuple(gallery_count.shape) != (N,) or not gallery_count.is_contiguous()):
@@ -153,8 +154,7 @@ class FeatureMoments:
         self.shift = self.n = self.s1 = self.s2 = None
 
     def add(self, x):
-        if torch.is_tensor(x) and not x.is_cuda:
-            raise L.ShotVaeHipError("FeatureMoments.add: input is not on an MI355X (no CPU fallback)")
+        on_device("FeatureMoments.add", x)
         if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != self.dim:
             raise ValueError("FeatureMoments.add: x must be a non-empty matrix [n, %d]" % self.dim)
         x = x.detach().double()
@@ -236,10 +236,7 @@ def evaluate_generation(model, batches, source="generate", space="mu", k=5, metr
     The generated images go back into the encoder as the model emits them, so the real images must be in the range the model
     reconstructs.  -> frechet (FeatureMoments / frechet_distance over the rows), precision, recall, density, coverage (manifold_metrics'
     definitions with `k`, `metric`), n.  Two host reads at the end: the integer sums and the moments."""
-    from .smooth import SmoothVAE
-    from .vae import VariationalAutoEncoder
-    if not isinstance(model, (VariationalAutoEncoder, SmoothVAE)):
-        raise TypeError("evaluate_generation: a VariationalAutoEncoder or a SmoothVAE, not %s" % type(model).__name__)
+    family = latent_family("evaluate_generation", model)
     if source not in ("generate", "reconstruct", "mixture"):
         raise ValueError("evaluate_generation: source must be 'generate', 'reconstruct' or 'mixture'")
     if (source == "mixture") != (mixture is not None):
@@ -248,7 +245,7 @@ def evaluate_generation(model, batches, source="generate", space="mu", k=5, metr
         raise ValueError("evaluate_generation: space must be 'mu' or 'features'")
     code = _ball_metric("evaluate_generation", metric)
     if space == "features":
-        if not isinstance(model, VariationalAutoEncoder):
+        if family != "shot":
             raise ValueError("evaluate_generation: space='features' needs a VariationalAutoEncoder (a SmoothVAE has no pooled features)")
         if code != L.DIST_EUCLID:
             raise ValueError("evaluate_generation: space='features' has no sigma: metric must be 'euclid'")
@@ -257,8 +254,7 @@ def evaluate_generation(model, batches, source="generate", space="mu", k=5, metr
         raise ValueError("evaluate_generation: k must be in [1, %d]" % MAX_K)
     if key is None:
         raise ValueError("evaluate_generation: the samples need a key")
-    if model.training:
-        raise NotImplementedError("evaluate_generation is implemented for eval mode only (no noise, no gradients): call model.eval() first")
+    eval_only("evaluate_generation", model)
 
     def rows_of(image):
         if space == "features":
@@ -269,14 +265,10 @@ def evaluate_generation(model, batches, source="generate", space="mu", k=5, metr
     real = fake = mom_real = mom_fake = None
     count = 0
     for batch in batches:
-        image, label = (batch[0], batch[1] if len(batch) > 1 else None) if isinstance(batch, (tuple, list)) else (batch, None)
-        for t in (image, label):
-            if torch.is_tensor(t) and not t.is_cuda:
-                raise L.ShotVaeHipError("evaluate_generation: input is not on an MI355X (no CPU fallback)")
+        image, label = split_batch("evaluate_generation", batch, False)
         if source in ("generate", "mixture"):
-            label = model.predict(image) if label is None else label.reshape(-1).long()
-            if label.numel() != image.shape[0]:
-                raise ValueError("evaluate_generation: %d labels for %d images" % (label.numel(), image.shape[0]))
+            if label is None:
+                label = model.predict(image)
             if source == "mixture":
                 from .mixture import generate_from_mixture
                 made = generate_from_mixture(model, mixture, label, key, row0=count)
