@@ -929,6 +929,48 @@ int sv_lp_step(const float* f_in, int M, const int64_t* rowptr, const int64_t* c
                void* stream);
 int sv_lp_finish(const float* f, int N, int K, float* proba, int64_t* pred, float* conf, int64_t* counts, void* stream);
 
+/* ---- kernel two-sample statistics: weighted kernel row sums for MMD, KID, witness and permutation test (ksum.hip) ----
+ * Added under ABI 8: new symbols only.  Rows are fp32 [rows][D] with row stride D.
+ *
+ * sv_ksum_scan: for each of S problems s, each query row i < Q and each partial state p < P
+ *       part[s][p][i] = sum_j w_j k(q_i, g_j)                                                          (double [S][P][Q], WRITTEN)
+ *   over the columns j of the gallery tiles p, p + P, .. (64 rows each) of the call, columns in index order within a tile and tiles in
+ *   order, every product (double) w_j * k and every addition rounded once in double, from 0.0.  A block that owns no tile writes 0.
+ *   Pair value: v(i, j) is THE VALUE sv_pairdist GIVES THE PAIR UNDER SV_DIST_EUCLID, bit for bit (direct differences, 16 dimensions in
+ *   fp32 with explicit fmaf in index order, the 16-blocks in double in index order, rounded once to fp32); u(i, j) is the dot product
+ *   by the same rule with part = fmaf(q, g, part).  kparam is a DEVICE array double [n_scale][2] = (a_s, b_s), shared by the S
+ *   problems; with x = (double) v or (double) u and every operation rounded once in double (no contraction):
+ *       SV_KSUM_RBF    k = sum_s b_s * exp(-(a_s * x))            in scale order from 0.0; 1 <= n_scale <= 8
+ *       SV_KSUM_IMQ    k = sum_s b_s / (1.0 + a_s * x)            in scale order from 0.0; 1 <= n_scale <= 8
+ *       SV_KSUM_POLY   k = b^degree, b = a_0 * x + b_0            r = b, then degree - 1 times r = r * b; n_scale == 1, 1 <= degree <= 8
+ *   g_w is fp32 [N] and may be NULL: every weight 1.  A column beyond N, a row beyond Q and the self pair col0 + j == self0 + i
+ *   (self0 = -1: none) are left out BY PREDICATE: k(q, 0) and 0 * NaN never enter a sum; a NaN or infinite row or weight reaches
+ *   exactly the sums that read it.  q_stride, g_stride (elements of q, g) and w_stride (elements of g_w) place problem s at
+ *   q + s q_stride, g + s g_stride, g_w + s w_stride; 0 shares the array among the problems, any other value must be at least the
+ *   array's size (Q D, N D, N).  The grid is ceil(Q / 64) x P x S blocks, 1 <= P <= 64, 1 <= S <= 65535.  Which pairs meet in which
+ *   state in which order is a function of the arguments alone: a repeated call gives the same bits; a gallery cut into calls
+ *   (col0, sv_ksum_finish's accumulate) changes the order of the additions.
+ *
+ * sv_ksum_finish:
+ *       row_sum[s][i] = (accumulate ? row_sum[s][i] + t : t),  t = part[s][0][i] + part[s][1][i] + .. in the order of p   (double [S][Q])
+ *       total[s]      = sum_i (double) q_w[s w_stride + i] * row_sum[s][i]                        (double [S]; NULL: no second launch)
+ *   q_w is fp32 and may be NULL: weights of 1 (w_stride as above, against Q).  total follows sv_lp_step's merge order: thread t of
+ *   256 adds the rows t, t + 256, .. in order from 0.0, then a binary tree over the threads (sh[t] += sh[t + h], h = 128 .. 1).  Both
+ *   outputs keep a NaN.
+ *
+ * Validated before any HIP call (SV_E_ARG / SV_E_SHAPE, nothing launched): an unknown kind; n_scale or degree out of range; NULL
+ * kparam, q, g, part or row_sum; q_w without total; Q, N or D < 1; S or P out of range; a stride that is neither 0 nor at least the
+ * array's size, or that overflows the index with S (SV_E_SHAPE); a negative col0; self0 < -1; col0 + N or self0 + Q beyond the index
+ * (SV_E_SHAPE).  Each takes a stream and allocates nothing: capturable; no atomic of any kind; nothing is read on the host.          */
+#define SV_KSUM_RBF 0
+#define SV_KSUM_IMQ 1
+#define SV_KSUM_POLY 2
+int sv_ksum_scan(int kind, const double* kparam, int n_scale, int degree, const float* q, int Q, int64_t q_stride, const float* g,
+                 const float* g_w, int N, int64_t g_stride, int64_t w_stride, int D, int S, int64_t col0, int64_t self0, int P,
+                 double* part, void* stream);
+int sv_ksum_finish(const double* part, int S, int P, int Q, int accumulate, double* row_sum, const float* q_w, int64_t w_stride,
+                   double* total, void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

@@ -26,4 +26,6 @@ from .embed import TSNE, conditional_affinities, symmetrize, pca_project, evalua
 from .mixture import GaussianMixture, evaluate_mixture, generate_from_mixture      # noqa: F401
 from .probe import LinearProbe, evaluate_probe, select_labels      # noqa: F401
 from .propagate import LabelPropagator, knn_graph, normalize_graph, evaluate_propagation      # noqa: F401
+from .twosample import (kernel_sums, median_bandwidth, mmd2, witness, kid, permutation_test, evaluate_two_sample,      # noqa: F401
+                        evaluate_prior_match, evaluate_kid)
 from .trace import StepLogger, step_range, enable_ranges     # noqa: F401

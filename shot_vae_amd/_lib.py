@@ -19,6 +19,7 @@ DIST_KL, DIST_W2, DIST_EUCLID, DIST_COSINE = 0, 1, 2, 3      # include/shotvae_h
 CAL_LOGIT, CAL_PROB = 0, 1                                    # include/shotvae_hip.h: SV_CAL_*
 LP_SYM, LP_ROW = 0, 1                                         # include/shotvae_hip.h: SV_LP_* (the normalisation)
 LP_SPREADING, LP_PROPAGATION, LP_PRODUCT = 0, 1, 2            # include/shotvae_hip.h: SV_LP_* (the variant of a step)
+KSUM_RBF, KSUM_IMQ, KSUM_POLY = 0, 1, 2                       # include/shotvae_hip.h: SV_KSUM_*
 
 
 class SvPhase(C.Structure):
@@ -200,6 +201,8 @@ _PROTOS = {
     "sv_lp_normalize": [P, P, P, I, I64, I, P, P, P],
     "sv_lp_step": [P, I, P, P, P, I64, I, I, P, I, C.c_double, C.c_double, P, P, P, P],
     "sv_lp_finish": [P, I, I, P, P, P, P, P],
+    "sv_ksum_scan": [I, P, I, I, P, I, I64, P, P, I, I64, I64, I, I, I64, I64, I, P, P],
+    "sv_ksum_finish": [P, I, I, I, I, P, P, I64, P, P],
     "sv_elbo_fwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P],
     "sv_elbo_bwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P, P, P, P, P],
     "sv_cls_fwd": [P, P, P, I, I, P, P],
