@@ -971,6 +971,62 @@ int sv_ksum_scan(int kind, const double* kparam, int n_scale, int degree, const 
 int sv_ksum_finish(const double* part, int S, int P, int Q, int accumulate, double* row_sum, const float* q_w, int64_t w_stride,
                    double* total, void* stream);
 
+/* ---- internal cluster validity: silhouette, and what Calinski-Harabasz and Davies-Bouldin need (validity.hip) ----
+ * Added under ABI 8: new symbols only.  Rows are fp32 [rows][D] with row stride D; labels and segment bounds are int64 ON THE DEVICE.
+ *
+ * sv_sil_scan: the gallery g [N][D] is GROUPED BY CLUSTER: with lo_c = clip(seg[c]), hi_c = clip(seg[c + 1]), clip(v) = min(max(v, 0), N),
+ *   cluster c < K is the rows lo_c .. hi_c - 1 of g and n_c = hi_c - lo_c (<= 0: the cluster is empty and is skipped).  Every bound is
+ *   clipped before use: a wrong seg gives wrong numbers, never a read outside g.  For each query row i < Q and partial state p < P
+ *       part_a[p][i] = T(i, q_label[i])                       if q_label[i] is one of the non-empty clusters p, p + P, .. < K;  else 0.0
+ *       part_b[p][i] = min over the OTHER non-empty clusters c (c != q_label[i]) among p, p + P, .. of  T(i, c) / (double) n_c,
+ *                      one double division per (row, cluster); +inf when there is none; a NaN among the means stays (a running minimum
+ *                      m = (v < m || v != v) ? v : m over the clusters in increasing order)                (double [P][Q], both WRITTEN)
+ *   T(i, c) = sum over the rows j of cluster c of (double) d(i, j), in THIS order: the cluster is cut into tiles of 64 rows from lo_c
+ *   (tile t = rows lo_c + 64 t ..; the first tile need not be aligned, a tile never crosses a cluster); the 16 threads of a row each
+ *   add the columns 4 tx .. 4 tx + 3 of every tile in index order, the tiles in order, from 0.0 -- thread tx's share --; at the end
+ *   of the cluster the 16 shares meet in the xor butterfly x += shfl_xor(x, 8), 4, 2, 1.  Every addition is rounded once in double.
+ *   Pair value: v(i, j) is THE VALUE sv_pairdist GIVES THE PAIR UNDER SV_DIST_EUCLID, bit for bit (direct differences, 16 dimensions in
+ *   fp32 with explicit fmaf in index order, the 16-blocks in double in index order, rounded once to fp32): a row is at distance exactly
+ *   0 from itself and from a duplicate.  d = v under SV_SIL_SQEUCLID, d = sqrtf(v) -- the correctly rounded fp32 root -- under
+ *   SV_SIL_EUCLID.  A column at or beyond hi_c and a row beyond Q are left out BY PREDICATE; a NaN or infinite gallery row reaches exactly
+ *   the (row, cluster) sums that read it.  A query row is taken to be a member of the gallery when q_label[i] is in [0, K): its own pair
+ *   (distance 0) is in T(i, q_label[i]) and sv_sil_finish divides by n - 1.  The grid is ceil(Q / 64) x P blocks, 1 <= P <= 64, 1 <= K <=
+ *   1024; a block whose p >= K owns no cluster and writes (0.0, +inf).
+ *
+ * sv_sil_finish: per row, with ta = part_a[0][i] + part_a[1][i] + .. in the order of p (one term is non-zero: exact for every P), tb =
+ *   the running minimum above over part_b[p][i] in the order of p, and n = n_c of c = q_label[i] (0 for a label outside [0, K)):
+ *       a[i] = ta / (double)(n - 1)    n > 1;      0.0    n == 1;      NaN    n < 1                        (double [Q], may be NULL)
+ *       b[i] = tb                                                                                          (double [Q], may be NULL)
+ *       s[i] = NaN                     n < 1, a or b NaN, b = +inf (no other non-empty cluster)  -- decided first
+ *            = 0.0                     n == 1 (a singleton), or max(a, b) == 0
+ *            = (b - a) / max(a, b)     otherwise: one subtraction, one division                             (double [Q])
+ *   Then, unless cluster_sum, cluster_cnt and skipped are NULL (all three or none), one block per cluster c < K in sv_ksum_finish's
+ *   merge order: thread t of 256 adds s[i] over the rows i = t, t + 256, .. with q_label[i] == c and s[i] not NaN, in order from 0.0,
+ *   then a binary tree over the threads (sh[t] += sh[t + h], h = 128 .. 1):
+ *       cluster_sum[c] (double [K]),  cluster_cnt[c] = the number of those rows (int64 [K]),  skipped[0] = the number of rows whose s is
+ *       NaN, whatever their label (int64 [1]).  All WRITTEN.  This pass reads K Q labels.
+ *
+ * sv_cluster_spread: rows x [N][D], label int64 [N] (any order), centroids c fp32 [K][D].
+ *       d2[i]      = THE VALUE sv_pairdist GIVES THE PAIR (x_i, c_label[i]) UNDER SV_DIST_EUCLID, bit for bit; NaN for a label outside
+ *                    [0, K)                                                                                (fp32 [N], may be NULL)
+ *       stat[k][0] = sum (double) d2[i],  stat[k][1] = sum (double) sqrtf(d2[i])  over the rows with label[i] == k, in the merge order
+ *                    above (thread t of 256: its rows t, t + 256, .. in order from 0.0; then the binary tree)        (double [K][2])
+ *       cnt[k]     = the number of those rows                                                              (int64 [K])
+ *   stat and cnt go together and may both be NULL.  A row that is not finite makes its cluster's stat NaN: give it a label of -1.
+ *
+ * Validated before any HIP call (SV_E_ARG, nothing launched): an unknown metric; NULL q, q_label, g, seg, part_a, part_b, s, x, label
+ * or c; cluster_sum, cluster_cnt, skipped not all or none; stat without cnt or the reverse; no output at all; Q, N or D < 1; K outside
+ * [1, 1024]; P outside [1, 64].  Each takes a stream and allocates nothing: capturable; no atomic of any kind; nothing is read on the
+ * host; a repeated call gives the same bits; s, a and b do not depend on P or on how the queries are cut into calls.               */
+#define SV_SIL_EUCLID 0
+#define SV_SIL_SQEUCLID 1
+int sv_sil_scan(int metric, const float* q, const int64_t* q_label, int Q, const float* g, const int64_t* seg, int N, int K, int D, int P,
+                double* part_a, double* part_b, void* stream);
+int sv_sil_finish(const double* part_a, const double* part_b, int P, int Q, const int64_t* q_label, const int64_t* seg, int K, int N,
+                  double* s, double* a, double* b, double* cluster_sum, int64_t* cluster_cnt, int64_t* skipped, void* stream);
+int sv_cluster_spread(const float* x, const int64_t* label, int N, int D, const float* c, int K, float* d2, double* stat, int64_t* cnt,
+                      void* stream);
+
 /* ---- K14/K15 smooth-ELBO terms (lib/criterion.py:32-57) -----------------------------------------
  * out3 = [recon, KL_c, KL_d] already divided by B (and 2*sigma^2 for MSE); must be zeroed by the
  * caller.  x / x_rec are NCHW fp32 (API edge).                                                      */

@@ -28,4 +28,6 @@ from .probe import LinearProbe, evaluate_probe, select_labels      # noqa: F401
 from .propagate import LabelPropagator, knn_graph, normalize_graph, evaluate_propagation      # noqa: F401
 from .twosample import (kernel_sums, median_bandwidth, mmd2, witness, kid, permutation_test, evaluate_two_sample,      # noqa: F401
                         evaluate_prior_match, evaluate_kid)
+from .validity import (silhouette_grouped, silhouette_samples, silhouette_score, cluster_spread, calinski_harabasz,      # noqa: F401
+                       davies_bouldin, validity_indices, evaluate_validity)
 from .trace import StepLogger, step_range, enable_ranges     # noqa: F401

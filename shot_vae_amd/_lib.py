@@ -20,6 +20,7 @@ CAL_LOGIT, CAL_PROB = 0, 1                                    # include/shotvae_
 LP_SYM, LP_ROW = 0, 1                                         # include/shotvae_hip.h: SV_LP_* (the normalisation)
 LP_SPREADING, LP_PROPAGATION, LP_PRODUCT = 0, 1, 2            # include/shotvae_hip.h: SV_LP_* (the variant of a step)
 KSUM_RBF, KSUM_IMQ, KSUM_POLY = 0, 1, 2                       # include/shotvae_hip.h: SV_KSUM_*
+SIL_EUCLID, SIL_SQEUCLID = 0, 1                               # include/shotvae_hip.h: SV_SIL_*
 
 
 class SvPhase(C.Structure):
@@ -203,6 +204,9 @@ _PROTOS = {
     "sv_lp_finish": [P, I, I, P, P, P, P, P],
     "sv_ksum_scan": [I, P, I, I, P, I, I64, P, P, I, I64, I64, I, I, I64, I64, I, P, P],
     "sv_ksum_finish": [P, I, I, I, I, P, P, I64, P, P],
+    "sv_sil_scan": [I, P, P, I, P, P, I, I, I, I, P, P, P],
+    "sv_sil_finish": [P, P, I, I, P, P, I, I, P, P, P, P, P, P, P],
+    "sv_cluster_spread": [P, P, I, I, P, I, P, P, P, P],
     "sv_elbo_fwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P],
     "sv_elbo_bwd": [P, P, I64, P, P, P, I, I, I, I, F, P, P, P, P, P, P],
     "sv_cls_fwd": [P, P, P, I, I, P, P],
